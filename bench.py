@@ -5,7 +5,7 @@ images/sec for the whole node, bs=64 per GPU, synthetic ImageNet, random-init we
 /root/reference/benchmark-scripts/run-tf-sing-ucx-openmpi.sh:62-113, ``-np TOTAL_WORKERS``
 at :99-109).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N=1: this process trains on cuda:0.
         N>1 without WORLD_SIZE in the environment: this process is only the launcher -- it
              starts N worker CHILD processes (one per MI355X, launch/launcher.py: rank env,
@@ -17,13 +17,35 @@ at :99-109).
 
 One process per MI355X; gradients averaged with RCCL over xGMI. The headline ``value`` is the
 reference's precision, fp32 (tf_cnn_benchmarks with MKL-DNN trains fp32: no --use_fp16 in
-run-tf-sing-ucx-openmpi.sh:62-81), on the hand-written HIP kernels; the same invocation then
-times the bf16 step and reports it as ``bf16_value`` / ``bf16_ms_per_step``. Per dtype: W
-untimed warmup steps (the first ones also capture the HIP graph), then EXACTLY K timed steps
-bracketed by barrier + device sync; the max time over ranks is used; rank 0 prints one JSON line
-that also carries ``world`` (torch.distributed) and ``rccl_nranks`` (read back from the native
-RCCL communicator), and every rank prints its own ``total images/sec`` lines on stderr. A native
-engine that fails its self-test at N>1 ends the run with exit code 5 (unless --engine torch).
+run-tf-sing-ucx-openmpi.sh:62-81), on the hand-written HIP kernels. A plain run does only what
+that figure needs: set up, W untimed warmup steps (the first ones also capture the HIP graph),
+then EXACTLY K timed steps bracketed by barrier + device sync; the max time over ranks is used;
+rank 0 prints one JSON line that also carries ``world`` (torch.distributed) and ``rccl_nranks``
+(read back from the native RCCL communicator), and every rank prints its own ``total images/sec``
+lines on stderr. A native engine that fails its self-test at N>1 ends the run with exit code 5
+(unless --engine torch).
+
+--full adds everything else the benchmark measures, each in runs of its own after the headline's
+timed steps: the bf16 step, timed the same way and reported as ``bf16_value`` /
+``bf16_ms_per_step`` (``--secondary auto``), and the communication profile of a data-parallel
+step (``comm``: allreduce time, exposed communication, overlap).
+
+--dump-outputs DIR writes what the timed path computes from the seeded start, as float32
+DIR/<name>.npy (rank 0): after the timed steps the training state (weights, momentum, BN
+statistics, loss-scale state) is set back to what it was before the warmup, the timed path -- the
+same captured graph -- runs one more step, and that last step's ``loss`` (the total_loss that
+step() returns) and the model it updated -- ``params`` (fp32 masters) and ``bn_buffers`` (BN
+moving statistics) -- are written, each whole or, above 4M elements, a fixed seeded sample of 4M
+elements in index order. Weights, images and labels are seeded, so two builds run with the same
+arguments compare output for output.
+
+Why the state is set back, and why only these arrays: the step sums in a hardware-scheduled order
+(split-K and BN-statistic atomics), and a random-init ResNet amplifies that last-bit noise through
+its 53 BN layers: two runs of ONE build from the same state differ after a single step by 3e-5 of
+the logits and 3e-2 of the gradient (relative L2), and the weights of the two runs drift apart
+step by step (after 20 + 5 fp32 ResNet-50 steps: params 2e-6, logits 1.5e-3, momentum 6e-2). One
+step from the seeded state repeats to the last bits of loss and params. HCB_DETERMINISTIC=1
+selects the single-writer kernels (14x slower), whose runs are bitwise equal.
 """
 from __future__ import annotations
 
@@ -60,16 +82,23 @@ def parse_args(argv=None):
                          "automatic loss scaling")
     ap.add_argument("--compute_dtype", default=None, choices=[None, "bf16", "fp16", "fp32"],
                     help="activation / GEMM precision of the reported value (default fp32 = the reference's "
-                         "precision, with bf16 timed as a secondary figure in the same run)")
+                         "precision; --full times bf16 as a secondary figure in the same run)")
     ap.add_argument("--secondary", default="auto", choices=["auto", "none", "bf16", "fp16", "fp32"],
                     help="a second compute dtype timed in the same run and reported as <dtype>_value "
-                         "(auto: bf16 when the primary is the default fp32, else none)")
+                         "(auto: bf16 under --full when the primary is the default fp32, else none)")
     ap.add_argument("--backward_segments", default="stage", choices=["stage", "block"],
                     help="gradient-reduction granularity of the overlapped multi-GPU step (ResNet): one segment "
                          "per stage, or per block in stages 3-4 with stage 1 split from the stem")
     ap.add_argument("--rccl_channels", type=int, default=None, help="NCCL_MIN/MAX_NCHANNELS for the workers")
     ap.add_argument("--rccl_algo", default=None, help="NCCL_ALGO for the workers (Ring, Tree)")
     ap.add_argument("--rccl_proto", default=None, help="NCCL_PROTO for the workers (Simple, LL, LL128)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own after its "
+                         "timed steps: the bf16 secondary figure (--secondary auto) and the communication "
+                         "profile of a data-parallel step")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (loss, updated parameters "
+                         "and BN moving statistics) as float32 DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -181,7 +210,29 @@ def _all_min_fn(world, dev):
     return all_min
 
 
-def run_model(args, dtype, world, rank, dev, reducer, all_min):
+DUMP_SAMPLE = 4 << 20  # elements per dumped array (16 MB as float32; three arrays stay far below 64 MB)
+
+
+def dump_outputs(path, trainer):
+    """--dump-outputs: what the last step run left its caller, as float32 ``path``/<name>.npy. An array
+    of more than DUMP_SAMPLE elements is written as a fixed sample: DUMP_SAMPLE indices drawn with a
+    seeded generator (the same for every run and build), in index order."""
+    import numpy as np
+    import torch
+
+    ps = trainer.ps
+    arrays = {"loss": trainer.loss, "params": ps.master, "bn_buffers": ps.buf}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20240229)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
+def run_model(args, dtype, world, rank, dev, reducer, all_min, dump=None):
     """Build, tune, warm up and time one model at one compute dtype; returns its result dict."""
     import torch
     import torch.distributed as dist
@@ -212,6 +263,9 @@ def run_model(args, dtype, world, rank, dev, reducer, all_min):
         if world > 1:
             dist.barrier()
 
+    # --dump-outputs: the state the run starts from (every rank: the extra step has collectives)
+    ps = model.ps
+    start = [(t, t.clone()) for t in (ps.master, ps.momentum, ps.buf, ps.persistbuf, trainer.hyper)] if dump else None
     warmup = max(args.warmup, 0)
     with tracing.range_(f"bench.warmup.{dtype}"):
         for _ in range(warmup):
@@ -235,11 +289,22 @@ def run_model(args, dtype, world, rank, dev, reducer, all_min):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = float(trainer.loss.item())
+    if dump:
+        # one more step of the timed path from the start state (at this step count's learning rate):
+        # what it computes repeats from run to run, what the drifted timed steps left does not
+        for t, c in start:
+            t.copy_(c)
+        trainer._lr_dev = None  # hyper was set back: the step rewrites the learning rate
+        trainer.step(images, labels)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(dump, trainer)
+        del start
     comm = None
     if reducer is not None:
         if hasattr(reducer, "check_errors"):
             reducer.check_errors()
-        if os.environ.get("HCB_BENCH_COMM_PROFILE", "1") == "1":  # after the timed region
+        if args.full and os.environ.get("HCB_BENCH_COMM_PROFILE", "1") == "1":  # after the timed region
             failed = 0
             try:  # restores the training state itself
                 comm = trainer.comm_profile(images, labels)
@@ -267,11 +332,24 @@ def run_model(args, dtype, world, rank, dev, reducer, all_min):
     return res
 
 
+def precisions(args):
+    """(primary, secondary) compute dtypes. The headline is measured at the reference's precision:
+    tf_cnn_benchmarks trains fp32 (MKL-DNN, run-tf-sing-ucx-openmpi.sh:62-81, no --use_fp16); under
+    --full the same invocation also times the bf16 step as a secondary figure."""
+    primary = args.compute_dtype or ("fp16" if args.use_fp16 else "fp32")
+    secondary = args.secondary if args.secondary != "auto" else (
+        "bf16" if (args.full and args.compute_dtype is None and not args.use_fp16) else "none")
+    return primary, secondary
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
     if args.gpus < 1:
         print("[bench] --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1:
+        print("[bench] --steps must be >= 1", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_workers(args, argv)
@@ -313,12 +391,7 @@ def main(argv=None):
     from azure_hc_intel_tf_amd.ops import _ext
 
     _ext.load()
-    # the headline is measured at the reference's precision: tf_cnn_benchmarks trains fp32
-    # (MKL-DNN, run-tf-sing-ucx-openmpi.sh:62-81, no --use_fp16); the same invocation also times
-    # the bf16 step as a secondary figure
-    primary = args.compute_dtype or ("fp16" if args.use_fp16 else "fp32")
-    secondary = args.secondary if args.secondary != "auto" else (
-        "bf16" if (args.compute_dtype is None and not args.use_fp16) else "none")
+    primary, secondary = precisions(args)
     all_min = _all_min_fn(world, dev)
     code, reducer, backend, rccl_nranks = init_comm(args, world, rank, dev, all_min)
     if code:
@@ -329,7 +402,7 @@ def main(argv=None):
 
         reducer = NativeReducer(compression=args.compression, force=True)
         rccl_nranks = reducer.comm.size()
-    results = [run_model(args, primary, world, rank, dev, reducer, all_min)]
+    results = [run_model(args, primary, world, rank, dev, reducer, all_min, dump=args.dump_outputs)]
     if secondary not in ("none", primary):
         results.append(run_model(args, secondary, world, rank, dev, reducer, all_min))
     main_r = results[0]

@@ -117,11 +117,48 @@ def test_native_engine_failure_is_a_nonzero_exit(monkeypatch):
 
 
 def test_default_headline_is_reference_precision():
-    """bench.py reports fp32 (the reference's MKL-DNN precision) as the headline value and times bf16
-    as the secondary figure in the same invocation."""
+    """bench.py reports fp32 (the reference's MKL-DNN precision) as the headline value and, with
+    --full, times bf16 as the secondary figure in the same invocation."""
     bench = _bench_module()
     a = bench.parse_args([])
-    assert a.compute_dtype is None and a.secondary == "auto" and not a.use_fp16
+    assert a.compute_dtype is None and a.secondary == "auto" and not a.use_fp16 and not a.full
     src = open(BENCH).read()
     assert 'primary = args.compute_dtype or ("fp16" if args.use_fp16 else "fp32")' in src
     assert 'res[f"{d}_value"]' in src
+    assert bench.precisions(bench.parse_args(["--full"])) == ("fp32", "bf16")
+
+
+def test_plain_run_times_the_headline_only():
+    """Without --full nothing but the headline is timed; an explicit --secondary still is."""
+    bench = _bench_module()
+    assert bench.precisions(bench.parse_args([])) == ("fp32", "none")
+    assert bench.precisions(bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])) == ("fp32", "none")
+    assert bench.precisions(bench.parse_args(["--full", "--compute_dtype", "bf16"])) == ("bf16", "none")
+    assert bench.precisions(bench.parse_args(["--full", "--use_fp16"])) == ("fp16", "none")
+    assert bench.precisions(bench.parse_args(["--secondary", "bf16"])) == ("fp32", "bf16")
+
+
+def test_dump_outputs_writes_float32_arrays_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array a float32 .npy; one above the element cap is the same seeded
+    sample (in index order) on every call."""
+    import types
+
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    n = 1000
+    ps = types.SimpleNamespace(master=torch.arange(n, dtype=torch.float32), buf=torch.ones(5, dtype=torch.float64))
+    tr = types.SimpleNamespace(ps=ps, loss=torch.tensor([2.5]))
+    bench.dump_outputs(str(tmp_path / "a"), tr)
+    bench.dump_outputs(str(tmp_path / "b"), tr)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["bn_buffers.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss.npy"].tolist() == [2.5] and got["bn_buffers.npy"].tolist() == [1.0] * 5
+    p = got["params.npy"]
+    assert p.shape == (100,) and (np.diff(p) >= 0).all() and 0 <= p.min() and p.max() < n
+    assert len(set(p.tolist())) > 50  # a spread sample, not one block
+    for f, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f))

@@ -14,9 +14,9 @@ run() {  # name, timeout, command...
   timeout -k 10 $t "$@" > gpurun_out/cfg_$name.log 2>&1 || { echo "$name failed"; tail -20 gpurun_out/cfg_$name.log; exit 1; }
   echo "== $name"; grep -E '^\{|total images/sec' gpurun_out/cfg_$name.log | tail -1 | cut -c1-400
 }
-run c2_resnet50_bs256 600 python bench.py --batch_size 256 --steps 20 --warmup 5
-run c3_resnet50_bs64 400 python bench.py --steps 50 --warmup 10
-run c4_inception3_bs64 600 python bench.py --model inception3 --batch_size 64 --steps 20 --warmup 5
+run c2_resnet50_bs256 600 python bench.py --full --batch_size 256 --steps 20 --warmup 5
+run c3_resnet50_bs64 400 python bench.py --full --steps 50 --warmup 10
+run c4_inception3_bs64 600 python bench.py --full --model inception3 --batch_size 64 --steps 20 --warmup 5
 run c5_resnet152_fp16_bs128 900 python tf_cnn_benchmarks.py --model=resnet152 --batch_size=128 --num_batches=30 \
     --num_warmup_batches=10 --display_every=10 --optimizer=momentum --variable_update=horovod --use_fp16 \
     --fp16_enable_auto_loss_scale --gradient_compression=fp16 --device=gpu

@@ -14,7 +14,7 @@ run() {  # name, timeout, command...
   tail -1 $OUT | cut -c1-200
 }
 if [ -z "$ZOO_ONLY" ]; then  # ZOO_ONLY=1: only the zoo rows (MODELS=" " / FP32_MODELS=" ": none of them)
-run c3_resnet50_bs64 300 python bench.py --steps 60 --warmup 10   # fp32 headline + bf16 secondary
+run c3_resnet50_bs64 300 python bench.py --full --steps 60 --warmup 10   # fp32 headline + bf16 secondary
 run c2_resnet50_bs256 400 python bench.py --batch_size 256 --compute_dtype bf16 --secondary none --steps 20 --warmup 5
 run c2_resnet50_bs256_fp32 400 python bench.py --batch_size 256 --compute_dtype fp32 --secondary none --steps 10 --warmup 3
 run c4_inception3_bs64 400 python bench.py --model inception3 --batch_size 64 --compute_dtype bf16 --secondary none \

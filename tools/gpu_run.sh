@@ -10,7 +10,8 @@
 #   smoke            __graft_entry__.smoke()
 #   tests[:files]    pytest -m gpu (whole suite, or the comma-separated files)
 #   bench[:args]     python bench.py (args comma-separated, e.g. bench:--batch_size=256)
-#   benchab:ENV      bench.py with and without ENV (e.g. benchab:HCB_X=0), interleaved 2 rounds
+#   benchab:ENV      bench.py --full (fp32 headline + bf16) with and without ENV (e.g. benchab:HCB_X=0),
+#                    interleaved 2 rounds
 #   convab:DIR       tools/conv_bench.py per-layer timings (CB_ARGS, default --fp32) with the in-tree
 #                    library and with the variant build DIR/_hcb_kernels.so (tools/build_variant.py)
 #   prof[:args]      rocprofv3 --kernel-trace --stats of bench.py, summarised by tools/kstats.py
@@ -51,7 +52,7 @@ for step in "$@"; do
     benchab)  # ABBA: base var var base (a drift between consecutive runs cancels)
       for r in 1 2; do if [ $r = 1 ]; then vs="base var"; else vs="var base"; fi; for v in $vs; do
         if [ $v = base ]; then e=""; else e="$args"; fi
-        env $e timeout -k 10 400 python bench.py --steps 40 --warmup 10 $BENCH_ARGS > ${O}_ab.json 2> ${O}_ab.err || fail benchab ${O}_ab.err
+        env $e timeout -k 10 400 python bench.py --full --steps 40 --warmup 10 $BENCH_ARGS > ${O}_ab.json 2> ${O}_ab.err || fail benchab ${O}_ab.err
         echo "$v [$e] $(python -c "import json;d=json.load(open('${O}_ab.json'));print(d['value'], d['ms_per_step'], 'bf16', d.get('bf16_value'), d.get('bf16_ms_per_step'))")"
       done; done ;;
     convab)
@@ -78,7 +79,7 @@ for step in "$@"; do
       timeout -k 10 400 python bench.py $common > ${O}_dp.json 2> ${O}_dp.err || fail dpsweep ${O}_dp.err
       echo "single-graph $(python tools/jfield.py ${O}_dp.json value ms_per_step)" | tee ${O}_dpsweep.txt
       for seg in stage block; do for mb in 32 64 128; do
-        HOROVOD_FUSION_THRESHOLD=$((mb << 20)) timeout -k 10 400 python bench.py $common --force_dp_path \
+        HOROVOD_FUSION_THRESHOLD=$((mb << 20)) timeout -k 10 400 python bench.py $common --full --force_dp_path \
           --backward_segments $seg > ${O}_dp.json 2> ${O}_dp.err || fail dpsweep ${O}_dp.err
         echo "dp seg=$seg bucket=${mb}MiB $(python tools/jfield.py ${O}_dp.json value ms_per_step comm)" \
           | tee -a ${O}_dpsweep.txt
