@@ -54,7 +54,8 @@ FLAGS: List[Flag] = [
     Flag("display_every", 10, int, "log cadence (steps)"),
     Flag("data_format", "NCHW", str, "logical layout (kernels run NHWC internally)", choices=["NCHW", "NHWC"]),
     Flag("optimizer", "sgd", str, "sgd | momentum", choices=["sgd", "momentum"]),
-    Flag("forward_only", False, parse_bool, "inference-only benchmark"),
+    Flag("forward_only", False, parse_bool, "inference-only benchmark (BN from the moving statistics, applied with "
+         "the residual add and ReLU in the conv GEMM's epilogue; HCB_FUSE_INFER_BN=0: separate BN passes)"),
     Flag("device", "gpu", str, "gpu (MI355X) or cpu", choices=["gpu", "cpu"]),
     Flag("mkl", False, parse_bool, "TF-MKL switch", noop_on_gpu=True),
     Flag("variable_update", "horovod", str, "horovod (RCCL data parallel) | replicated (single process)",

@@ -92,6 +92,17 @@ FUSE_RES_BN = True
 # layer's previous batch mean, so E[x^2] - E[x]^2 does not cancel in fp32 when |mean| >> std
 # (False: K = 0, the plain single-pass form)
 BN_SHIFT = True
+# forward-only (inference) conv + BN layers: the BN affine step, the residual add and the ReLU run in
+# the conv GEMM's epilogue (Fn.conv_bn_inference: one launch, the output written once in the next
+# GEMM's operand format, no raw conv output); False (HCB_FUSE_INFER_BN=0): conv_forward + bn_inference
+def _env_on(name: str) -> bool:
+    """A default-on switch read from the environment (``NAME=0`` turns it off)."""
+    return os.environ.get(name, "1") != "0"
+
+
+FUSE_INFER_BN = _env_on("HCB_FUSE_INFER_BN")
+
+
 class _FixedParam:
     """A non-trainable per-channel constant with a scratch gradient sink (BN scale=False)."""
 
@@ -220,6 +231,13 @@ class ConvBN(Layer):
         N = x.shape[0]
         P, Q, C = self.out_shape
         dev = x.device
+        if self.bn and not self.training and FUSE_INFER_BN:
+            y = out if out is not None else empty_op((N, P, Q, C), dev)
+            Fn.conv_bn_inference(x, self.spec, self.pack.pack if Fn.native(x) else None, self.w.data,
+                                 self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
+                                 self.relu, residual=residual)
+            self._saved = None
+            return y
         if self.bn and not self.training:
             z = empty_act((N, P, Q, C), dev)
             y = out if out is not None else empty_act((N, P, Q, C), dev)
@@ -531,6 +549,13 @@ class StemS2D(ConvBN):
             return super().forward(x, out, residual)
         N = x.shape[0]
         P, Q, C = self.out_shape
+        if not self.training and FUSE_INFER_BN:
+            y = out if out is not None else empty_op((N, P, Q, C), x.device)
+            Fn.conv_bn_inference(self.fold_input(x), self.fold_spec, self._folded_weight(x.device), self.w.data,
+                                 self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
+                                 self.relu, residual=residual)
+            self._saved = None
+            return y
         z = empty_act((N, P, Q, C), x.device)
         y = out if out is not None else empty_act((N, P, Q, C), x.device)
         if not self.training:

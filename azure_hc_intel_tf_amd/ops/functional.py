@@ -301,6 +301,9 @@ _CONV_TILES = {0: (128, 128), 1: (128, 64), 2: (64, 64), 3: (64, 128),
 # round 5: profiles/r5_prune_variants.txt)
 PATCH_CFG0 = 17
 PATCH_CFGS = (17, 18, 19, 20, 21)
+# the LDS-DMA kernel of the same row tile that serves a problem the patch kernels do not
+# (conv_igemm.hip launch_conv_igemm's fallback table)
+_PATCH_TWIN = {17: 13, 18: 14, 19: 14, 20: 5, 21: 13}
 # weight-grad cfg -> (Nout tile, K tile); 0-2 register-staged, 3-14 LDS-DMA rings
 _WGRAD_TILES = {0: (128, 128), 1: (64, 128), 2: (64, 64), 3: (128, 128), 4: (128, 128), 5: (256, 128),
                 6: (128, 256), 7: (64, 128), 8: (64, 64), 9: (64, 128), 10: (64, 64), 11: (128, 64),
@@ -922,9 +925,59 @@ class BNSaved:
         self.invstd = invstd
 
 
+def conv_bn_inference(x, spec: ConvSpec, wpack, w_master, gamma, beta, running_mean, running_var, eps, out,
+                      relu: bool, residual=None, cfg=None):
+    """Inference conv + BN (``--forward_only``) in one pass: out = act(scale*conv(x, W) + shift [+ res])
+    with scale = gamma/sqrt(moving_var+eps), shift = beta - moving_mean*scale. GPU native: ONE launch,
+    the GEMM's inference epilogue (csrc/kernels/igemm_epilogue.h INF) derives (scale, shift) from the
+    live parameter tensors at kernel start -- nothing is computed on the host or cached, so a captured
+    graph sees moving statistics changed since capture -- and writes the consumer's operand: 16-bit,
+    or on the fp32 path Planes (``out`` Planes) or fp32; no raw conv output is stored. ``residual`` is
+    read in ``out``'s format (converted once when it arrives in the other one). ``cfg``: None (the
+    forward plan), an int or (cfg, splits); a cfg without the inference epilogue (the persistent /
+    stream-K / weights-resident plane GEMMs, the 3x3 patch kernels) runs its per-tile twin. CPU and
+    GPU non-native: exactly conv_forward followed by bn_inference."""
+    N, H, W, _ = x.shape
+    P, Q = spec.out_hw(H, W)
+    M = N * P * Q
+    p3 = is_planes(x) or (native(x) and x.dtype == torch.float32)
+    if not p3 and not native(x):
+        z = torch.empty((N, P, Q, spec.cout), dtype=out.dtype, device=x.device)
+        conv_forward(x, spec, wpack, w_master, z)
+        return bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu, residual=residual)
+    if p3:
+        x = to_planes(x)
+        if residual is not None:  # the epilogue reads a residual in out's format (fp32, or planes)
+            residual = to_planes(residual) if is_planes(out) else from_planes(residual)
+        cfg, splits = _plan3(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw)
+        if cfg in _P3_PERSIST:
+            cfg = _P3_PERSIST[cfg]
+        w_lo = lo_pack(wpack)
+        assert w_lo is not None and out.dtype == torch.float32, "fp32 conv needs the mid / lo weight packs"
+    else:
+        cfg, splits = _plan(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw)
+        if cfg in PATCH_CFGS:  # no split-K on the twin, as launch_conv_igemm's own fallback
+            cfg, splits = _PATCH_TWIN[cfg], 1
+    if residual is not None:
+        assert ld(residual) == ld(out) and residual.shape == out.shape and residual.dtype == out.dtype
+    geom = [N, H, W, spec.cin_pad, ld(x), P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
+            spec.dh, spec.dw, 1, 1, spec.cout, spec.K, spec.Kpad, ld(out), 0, P, Q, 1, 1,
+            1 if residual is not None else 0, 0 if is_planes(out) else _f32o(out), 1 if relu else 0, 0, splits]
+    if p3:
+        _ext.ops().conv_p3_inf(x.t, wpack, w_lo, _pl(out), _pl(residual), geom, cfg, gamma, beta, running_mean,
+                               running_var, float(eps))
+    else:
+        _ext.ops().conv_igemm_inf(x, wpack, out, residual, geom, cfg, gamma, beta, running_mean, running_var,
+                                  float(eps))
+    return out
+
+
 def bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu: bool, residual=None):
     """Inference BN (``--forward_only``: tf_cnn_benchmarks builds the model with
-    phase_train=False): out = act(gamma*(z-moving_mean)/sqrt(moving_var+eps) + beta [+ res])."""
+    phase_train=False): out = act(gamma*(z-moving_mean)/sqrt(moving_var+eps) + beta [+ res]).
+    A BN without a producing GEMM (ResNet v2's pre-activation, ``BNReLU``) and the unfused form of
+    conv + BN layers (``nn.layers.FUSE_INFER_BN`` off); with the switch on those layers run
+    conv_bn_inference, which applies the same affine step in the GEMM epilogue."""
     N, H, W, C = z.shape
     if native(z) and z.dtype == torch.float32:
         # fp32 path: the fp32 apply kernel of training (bn_apply_acc, z / out / residual fp32) fed

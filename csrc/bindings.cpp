@@ -291,6 +291,41 @@ void conv_igemm_bnb(const Tensor& x, const Tensor& w, const Tensor& y, const c10
   hcb::launch_conv_igemm(p, (int)cfg, cur_stream());
 }
 
+// the inference-epilogue fields of a forward GEMM (ConvParams::inf): the four live BN vectors and eps;
+// the residual (p.beta, validated by conv_params against y's format, rows and ldy) stays in p.yres
+void set_inf(hcb::ConvParams& p, const Tensor& y, const Tensor& gamma, const Tensor& beta, const Tensor& mean,
+             const Tensor& var, double eps) {
+  TORCH_CHECK(p.bias == nullptr && p.stats == nullptr && p.remap == 0 && p.idil_h == 1 && p.idil_w == 1,
+              "hcb.conv_inf: a forward conv without bias / statistics / remap / lhs dilation");
+  TORCH_CHECK(eps > 0.0, "hcb.conv_inf: eps > 0");
+  for (const Tensor* t : {&gamma, &beta, &mean, &var}) {
+    check_f32(*t, "bn param");
+    TORCH_CHECK(t->dim() == 1 && t->numel() == p.Nout && t->is_contiguous() && t->device() == y.device(),
+                "hcb.conv_inf: gamma / beta / moving mean / moving variance must be fp32 [cout] on the output's device");
+  }
+  p.bnb_gamma = gamma.data_ptr<float>();
+  p.bnb_beta = beta.data_ptr<float>();
+  p.bnb_mean = mean.data_ptr<float>();
+  p.bnb_invstd = var.data_ptr<float>();  // the moving variance (see ConvParams::inf)
+  p.inf = 1;
+  p.inf_eps = (float)eps;
+}
+
+// forward conv + inference BN (+ residual, ReLU) in the GEMM epilogue: y = act(scale * conv(x, w) +
+// shift [+ res]), 16-bit y; geom as conv_igemm (beta = 1: res is read, in y's format and ldy)
+void conv_igemm_inf(const Tensor& x, const Tensor& w, const Tensor& y, const c10::optional<Tensor>& res,
+                    at::IntArrayRef g, int64_t cfg, const Tensor& gamma, const Tensor& beta, const Tensor& mean,
+                    const Tensor& var, double eps) {
+  TORCH_CHECK(cfg >= 0 && cfg <= 16, "hcb.conv_igemm_inf: cfg 0..16 (a patch cfg runs its LDS-DMA twin)");
+  hcb::ConvParams p = conv_params(x, w, y, res, c10::nullopt, c10::nullopt, g, cfg);
+  TORCH_CHECK(x.scalar_type() != at::kFloat && !p.out_f32,
+              "hcb.conv_igemm_inf: 16-bit operands and output (fp32 runs on the plane GEMMs: hcb.conv_p3_inf)");
+  TORCH_CHECK(!p.beta || res->scalar_type() == y.scalar_type(), "hcb.conv_igemm_inf: res dtype differs from y");
+  p.w_lo = p.w_lo2 = nullptr;
+  set_inf(p, y, gamma, beta, mean, var, eps);
+  hcb::launch_conv_igemm(p, (int)cfg, cur_stream());
+}
+
 int64_t conv_tiles_m(int64_t M, int64_t cfg) {
   int t = hcb::conv_tile_m((int)cfg);
   return (M + t - 1) / t;
@@ -1078,10 +1113,12 @@ void stem_wgrad_unfold(const Tensor& dwp, const Tensor& dw) {
 // ---- fp32 path on bf16 planes (conv_p3.hip)
 
 // geom as conv_igemm; x: planes of the input, w: hi pack, w_lo: [2][n] mid / lo packs; y fp32
+// (y_planes, the inference epilogue's plane output: y / yres are plane 0 of the output / residual
+// planes, validated as 16-bit tensors with geom's out_f32 = 0)
 hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Tensor& y,
                           const c10::optional<Tensor>& yres, const c10::optional<Tensor>& bias,
                           const c10::optional<Tensor>& stats, at::IntArrayRef g, int64_t cfg,
-                          const c10::optional<Tensor>& stats_shift) {
+                          const c10::optional<Tensor>& stats_shift, bool y_planes = false) {
   const int64_t xps = check_planes(x, "x");
   TORCH_CHECK(cfg >= 0 && cfg < 37, "hcb.conv_p3: cfg 0..36");
   // conv_params validates geometry and byte ranges on plane 0 (a bf16 tensor of this build's type);
@@ -1094,7 +1131,8 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
   const int64_t tiles = (int64_t)((p.M + bm - 1) / bm) * ((p.Nout + bn - 1) / bn);
   p.splits = (int)splits;
   TORCH_CHECK(p.splits >= 1 && p.splits <= p.Kpad / 64, "hcb.conv_p3: 1 <= splits <= k-steps");
-  TORCH_CHECK(p.out_f32 && y.scalar_type() == at::kFloat, "hcb.conv_p3: fp32 output");
+  TORCH_CHECK(y_planes ? !p.out_f32 : p.out_f32 && y.scalar_type() == at::kFloat,
+              "hcb.conv_p3: fp32 output (geom out_f32 = 0 with a plane output)");
   check_range(x, 2 * xps * 2 + (int64_t)p.x_bytes, "x planes");
   TORCH_CHECK(2 * xps * 2 < (1ll << 32), "hcb.conv_p3: plane stride exceeds the 32-bit offset range");
   p.x_plane = (uint32_t)(xps * 2);
@@ -1148,6 +1186,43 @@ void conv_p3_bnb(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Ten
                  const Tensor& gamma, const Tensor& beta, const Tensor& acc, int64_t R, int64_t mode) {
   hcb::ConvParams p = p3_params(x, w, w_lo, y, yres, c10::nullopt, c10::nullopt, g, cfg, c10::nullopt);
   set_bnb(p, z, yact, ld, mean, invstd, gamma, beta, acc, R, mode, true);
+  hcb::launch_conv_p3(p, (int)cfg, cur_stream());
+}
+
+// fp32 forward conv + inference BN (+ residual, ReLU) in the plane GEMM's epilogue (see
+// conv_igemm_inf): y fp32 (geom out_f32 = 1), or bf16 planes [3, ...] (out_f32 = 0) written with the
+// output's plane stride; res in y's format. cfg 0..17: the per-tile kernels.
+void conv_p3_inf(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Tensor& y,
+                 const c10::optional<Tensor>& res, at::IntArrayRef g, int64_t cfg, const Tensor& gamma,
+                 const Tensor& beta, const Tensor& mean, const Tensor& var, double eps) {
+  TORCH_CHECK(cfg >= 0 && cfg <= 17, "hcb.conv_p3_inf: cfg 0..17 (a persistent cfg runs its per-tile twin)");
+  TORCH_CHECK(g.size() >= 28, "hcb.conv_p3_inf: geom");
+  const bool yp3 = y.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(yp3 == (g[27] == 0), "hcb.conv_p3_inf: geom out_f32 = 0 exactly for a plane output");
+  hcb::ConvParams p;
+  if (yp3) {
+    const int64_t yps = check_planes(y, "y");
+    c10::optional<Tensor> r0;
+    int64_t rps = 0;
+    if (g[26]) {
+      TORCH_CHECK(res.has_value(), "hcb.conv_p3_inf: beta needs res");
+      rps = check_planes(*res, "res");
+      r0 = res->select(0, 0);
+    }
+    p = p3_params(x, w, w_lo, y.select(0, 0), r0, c10::nullopt, c10::nullopt, g, cfg, c10::nullopt, true);
+    // conv_params checked plane 0's rows against the storage; the other two planes lie 2 * stride on
+    const int64_t span = ((int64_t)(p.M - 1) * p.ldy + ((p.Nout + 7) / 8) * 8) * 2;
+    check_range(y, 2 * yps * 2 + span, "y planes");
+    TORCH_CHECK(yps >= span / 2, "hcb.conv_p3_inf: y planes overlap");
+    if (p.beta) check_range(*res, 2 * rps * 2 + span, "res planes");
+    p.y_p3 = 1;
+    p.y_plane = yps;
+    p.yres_plane = rps;
+  } else {
+    TORCH_CHECK(!g[26] || (res.has_value() && res->scalar_type() == at::kFloat), "hcb.conv_p3_inf: fp32 res");
+    p = p3_params(x, w, w_lo, y, res, c10::nullopt, c10::nullopt, g, cfg, c10::nullopt);
+  }
+  set_inf(p, y, gamma, beta, mean, var, eps);
   hcb::launch_conv_p3(p, (int)cfg, cur_stream());
 }
 
@@ -1237,6 +1312,7 @@ void set_deterministic(bool on) { hcb::set_deterministic(on); }
 HCB_TORCH_LIBRARY(hcb, m) {
   m.def("conv_igemm(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, Tensor? bias, Tensor(b!)? stats, int[] geom, int cfg, Tensor? stats_shift=None, Tensor? w_lo=None) -> ()");
   m.def("conv_igemm_bnb(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, int[] geom, int cfg, Tensor z, Tensor? yact, int ld, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor(b!) acc, int R, int mode) -> ()");
+  m.def("conv_igemm_inf(Tensor x, Tensor w, Tensor(a!) y, Tensor? res, int[] geom, int cfg, Tensor gamma, Tensor beta, Tensor mean, Tensor var, float eps) -> ()");
   m.def("conv_tiles_m(int M, int cfg) -> int", conv_tiles_m);
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
   m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);
@@ -1287,6 +1363,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("conv_p3(Tensor x, Tensor w, Tensor w_lo, Tensor(a!) y, Tensor? yres, Tensor? bias, Tensor(b!)? stats, int[] geom, int cfg, Tensor? stats_shift=None) -> ()");
   m.def("conv_wgrad_p3(Tensor dy, Tensor x, Tensor(a!) dw, int[] geom, int cfg, int splits) -> ()");
   m.def("conv_p3_bnb(Tensor x, Tensor w, Tensor w_lo, Tensor(a!) y, Tensor? yres, int[] geom, int cfg, Tensor z, Tensor? yact, int ld, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor(b!) acc, int R, int mode) -> ()");
+  m.def("conv_p3_inf(Tensor x, Tensor w, Tensor w_lo, Tensor(a!) y, Tensor? res, int[] geom, int cfg, Tensor gamma, Tensor beta, Tensor mean, Tensor var, float eps) -> ()");
   m.def("split_planes(Tensor x, int ldx, int rows, int C, Tensor(a!) out, int ldo) -> ()");
   m.def("merge_planes(Tensor x, int ldi, int rows, int C, Tensor(a!) y, int ldy) -> ()");
   m.def("gap_fwd_p3(Tensor x, Tensor(a!) y, int N, int HW, int C) -> ()");
@@ -1295,6 +1372,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
 HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("conv_igemm", conv_igemm);
   m.impl("conv_igemm_bnb", conv_igemm_bnb);
+  m.impl("conv_igemm_inf", conv_igemm_inf);
   m.impl("nonfinite", nonfinite);
   m.impl("loss_total", loss_total);
   m.impl("loss_scale_update", loss_scale_update);
@@ -1339,6 +1417,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("conv_p3", conv_p3);
   m.impl("conv_wgrad_p3", conv_wgrad_p3);
   m.impl("conv_p3_bnb", conv_p3_bnb);
+  m.impl("conv_p3_inf", conv_p3_inf);
   m.impl("split_planes", split_planes);
   m.impl("merge_planes", merge_planes);
   m.impl("gap_fwd_p3", gap_fwd_p3);

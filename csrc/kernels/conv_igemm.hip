@@ -114,7 +114,8 @@ __device__ __forceinline__ void mfma_tile_step(const u32x4* Ab, const u32x4* Bb,
 
 // ============================================================== register-staged main loop
 // (16-bit operands; fp32 runs on the plane GEMMs, conv_p3.hip)
-template <int WM, int WN, int TM, int TN, bool CBIG, bool LHSDIL, bool BNB>
+// INF: the inference epilogue (forward-only conv + BN; igemm_epilogue.h)
+template <int WM, int WN, int TM, int TN, bool CBIG, bool LHSDIL, bool BNB, bool INF = false>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
   constexpr int BM = WM * TM, BN = WN * TN, BK = 64;
   constexpr int MI = TM / 16, NI = TN / 16;
@@ -177,6 +178,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
   pre.load_shift(p, n0, wn, lane);
   constexpr size_t PARAM_OFF = reg_param_off(BM, BN, WM);
   if constexpr (BNB) stage_bnb_params<BN, 256>(p, n0, smem + PARAM_OFF);  // published by the first barrier
+  if constexpr (INF) stage_inf_params<BN, 256>(p, n0, smem + PARAM_OFF);
   const bool early = BNB && nk <= EARLY_EPI_KSTEPS;
   if (early) pre.load(p, 0, m0, n0, tid);
   gload(0);
@@ -189,7 +191,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     if (kt + 1 < nk) lstore(cur ^ 1);
     __syncthreads();
   }
-  igemm_epilogue<WM, WN, TM, TN, BNB>(p, acc, smem, tm, m0, n0, wm, wn, lane, tid, pre, early, smem + PARAM_OFF);
+  igemm_epilogue<WM, WN, TM, TN, BNB, false, INF>(p, acc, smem, tm, m0, n0, wm, wn, lane, tid, pre, early,
+                                                  smem + PARAM_OFF);
 }
 
 // ============================================================== LDS-DMA multi-stage main loop
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
 // ilv_schedule, +1.4% fp32 -- measured neutral here: bf16 9,698-9,704 vs 9,707-9,728 img/s,
 // profiles/r5_prune_variants.txt; the register-pipelined, two-k-step and occupancy-ring variants of
 // this loop were removed in round 5 for the same reason.)
-template <int WM, int WN, int TM, int TN, int NST, bool CBIG, bool LHSDIL, bool BNB>
+template <int WM, int WN, int TM, int TN, int NST, bool CBIG, bool LHSDIL, bool BNB, bool INF = false>
 __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void conv_igemm_glds_kernel(ConvParams p) {
   constexpr int BM = WM * TM, BN = WN * TN;
   constexpr int MI = TM / 16, NI = TN / 16;
@@ -260,8 +263,9 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void conv_igemm_glds_ker
   EpiPrefetch<WM, WN, TM, TN, BNB> pre;
   pre.load_shift(p, n0, wn, lane);
   constexpr size_t PARAM_OFF = glds_param_off(BM, BN, WM, NST);
-  constexpr bool PARAM_LDS = PARAM_OFF + bnb_param_lds(BN) <= 160 * 1024;
+  constexpr bool PARAM_LDS = PARAM_OFF + (INF ? inf_param_lds(BN) : bnb_param_lds(BN)) <= 160 * 1024;
   if constexpr (BNB && PARAM_LDS) stage_bnb_params<BN, NT>(p, n0, smem + PARAM_OFF);  // published by the first barrier
+  if constexpr (INF && PARAM_LDS) stage_inf_params<BN, NT>(p, n0, smem + PARAM_OFF);
   const bool early = BNB && S == 1 && nk <= EARLY_EPI_KSTEPS;
   if (early) pre.load(p, 0, m0, n0, tid);
 #pragma unroll
@@ -290,8 +294,8 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void conv_igemm_glds_ker
   }
   __syncthreads();  // every wave is done reading the ring before the epilogue reuses LDS
   if (S > 1 && !splitk_gather<MI, NI, NT>(p, acc, smem, tile, split, S, tid)) return;
-  igemm_epilogue<WM, WN, TM, TN, BNB>(p, acc, smem, tm, m0, n0, wm, wn, lane, tid, pre, early,
-                                      PARAM_LDS ? smem + PARAM_OFF : nullptr);
+  igemm_epilogue<WM, WN, TM, TN, BNB, false, INF>(p, acc, smem, tm, m0, n0, wm, wn, lane, tid, pre, early,
+                                                  PARAM_LDS ? smem + PARAM_OFF : nullptr);
 }
 
 // ============================================================== launch
@@ -365,6 +369,46 @@ static void launch_glds(const ConvParams& p, hipStream_t st) {
     hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, true, BNB>), dim3(tiles), dim3(NT), lds, st, p);
 }
 
+// The inference-epilogue instantiations (forward problems only: no lhs dilation). Their LDS is the
+// ring / staging extent plus the (scale, shift) table; a ring that fills LDS (cfg 9) loads the
+// coefficients from global memory instead.
+template <int WM, int WN, int TM, int TN>
+static void launch_reg_inf(const ConvParams& p, hipStream_t st) {
+  constexpr int BM = WM * TM, BN = WN * TN;
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN);
+  const size_t lds = reg_param_off(BM, BN, WM) + inf_param_lds(BN);
+  static bool once = false;
+  if (!once) {
+    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, true, false, false, true>);
+    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, false, false, false, true>);
+    once = true;
+  }
+  if ((p.C % 64) == 0)
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false, false, true>), dim3(tiles), dim3(256), lds, st, p);
+  else
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false, false, true>), dim3(tiles), dim3(256), lds, st, p);
+}
+
+template <int WM, int WN, int TM, int TN, int NST>
+static void launch_glds_inf(const ConvParams& p, hipStream_t st) {
+  constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64;
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
+  constexpr size_t OFF = glds_param_off(BM, BN, WM, NST);
+  const size_t lds = OFF + inf_param_lds(BN) <= 160 * 1024 ? OFF + inf_param_lds(BN) : OFF;
+  static bool once = false;
+  if (!once) {
+    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, false, false, true>);
+    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, false, false, true>);
+    once = true;
+  }
+  if ((p.C % 64) == 0)
+    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, false, false, true>), dim3(tiles), dim3(NT),
+                       lds, st, p);
+  else
+    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, false, false, true>), dim3(tiles), dim3(NT),
+                       lds, st, p);
+}
+
 // cfg: 0..3 register-staged {128x128, 128x64, 64x64, 64x128}; 4..7 the same tiles on the
 // LDS-DMA ring (NST 3, 3, 4, 3); 8..11 deeper rings for latency-bound few-tile layers
 // (128x128 NST 4 and 5, 128x64 NST 6, 64x128 NST 6); 12..16 eight-wave workgroups (two
@@ -410,7 +454,34 @@ static void launch_cfg(const ConvParams& p, int cfg, hipStream_t st) {
   }
 }
 
+// cfg 0-16 as launch_cfg
+static void launch_inf_cfg(const ConvParams& p, int cfg, hipStream_t st) {
+  switch (cfg) {
+    case 1: launch_reg_inf<4, 1, 32, 64>(p, st); break;
+    case 2: launch_reg_inf<2, 2, 32, 32>(p, st); break;
+    case 3: launch_reg_inf<1, 4, 64, 32>(p, st); break;
+    case 4: launch_glds_inf<2, 2, 64, 64, 3>(p, st); break;
+    case 5: launch_glds_inf<4, 1, 32, 64, 3>(p, st); break;
+    case 6: launch_glds_inf<2, 2, 32, 32, 4>(p, st); break;
+    case 7: launch_glds_inf<1, 4, 64, 32, 3>(p, st); break;
+    case 8: launch_glds_inf<2, 2, 64, 64, 4>(p, st); break;
+    case 9: launch_glds_inf<2, 2, 64, 64, 5>(p, st); break;
+    case 10: launch_glds_inf<4, 1, 32, 64, 6>(p, st); break;
+    case 11: launch_glds_inf<1, 4, 64, 32, 6>(p, st); break;
+    case 12: launch_glds_inf<2, 4, 64, 32, 3>(p, st); break;
+    case 13: launch_glds_inf<4, 2, 32, 64, 3>(p, st); break;
+    case 14: launch_glds_inf<4, 2, 64, 64, 3>(p, st); break;
+    case 15: launch_glds_inf<2, 4, 64, 64, 3>(p, st); break;
+    case 16: launch_glds_inf<2, 4, 32, 32, 4>(p, st); break;
+    default: launch_reg_inf<2, 2, 64, 64>(p, st); break;
+  }
+}
+
 void launch_conv_igemm(const ConvParams& p, int cfg, hipStream_t st) {
+  if (p.inf) {  // the inference epilogue: cfg 0-16 (checked by the binding; no patch kernels)
+    launch_inf_cfg(p, cfg, st);
+    return;
+  }
   if (cfg >= CONV_PATCH_CFG0 && cfg < CONV_PATCH_CFG0 + 5) {
     if (launch_conv3x3_patch(p, cfg, st)) return;
     // not a 3x3 / stride-1 problem (or its patch does not fit LDS): an LDS-DMA kernel of the

@@ -77,6 +77,10 @@ static int launch_p3_persist(const ConvParams& p, int cfg, hipStream_t st) {
 void set_p3p_bnb(int v) { p3p_bnb_level() = v; }
 
 void launch_conv_p3(const ConvParams& p, int cfg, hipStream_t st) {
+  if (p.inf) {  // the inference epilogue: per-tile kernels only (cfg 0-17, checked by the binding)
+    launch_p3_inf_cfg(p, cfg, st);
+    return;
+  }
   if (cfg >= 18 && (cfg = launch_p3_persist(p, cfg, st)) < 0) return;
   if (p.bnb_acc != nullptr)
     launch_p3_cfg<true>(p, cfg, st);

@@ -103,7 +103,10 @@ template <int OCC, int NW>
 constexpr int p3_regs_per_wave() {
   return 512 / (OCC * NW / 4 > 0 ? OCC * NW / 4 : 1);
 }
-template <int WM, int WN, int TM, int TN, int KW, int NST, bool CBIG, bool LHSDIL, bool BNB, int OCC = 1>
+// INF: the inference epilogue (forward-only conv + BN: act(scale * acc + shift [+ residual]), fp32 or
+// plane output; igemm_epilogue.h), its (scale, shift) table staged where BNB stages its parameters
+template <int WM, int WN, int TM, int TN, int KW, int NST, bool CBIG, bool LHSDIL, bool BNB, int OCC = 1,
+          bool INF = false>
 __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_igemm_p3_kernel(ConvParams p) {
   constexpr int BM = WM * TM, BN = WN * TN;
   constexpr int MI = TM / 16, NI = TN / 16;
@@ -186,6 +189,7 @@ __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_igemm_p3_ke
   pre.load_shift(p, n0, wn, lane);
   constexpr size_t PARAM_OFF = p3_param_off<BM, BN, WM, KW, NST>();
   if constexpr (BNB) stage_bnb_params<BN, NT>(p, n0, smem + PARAM_OFF);  // published by the first barrier
+  if constexpr (INF) stage_inf_params<BN, NT>(p, n0, smem + PARAM_OFF);
   const bool early = BNB && parts == 1 && nk * KW <= EARLY_EPI_KSTEPS_P3 * 64;
   if (early) pre.load(p, 0, m0, n0, tid);
 #pragma unroll
@@ -249,8 +253,8 @@ __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_igemm_p3_ke
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dummy pieces have landed before LDS reuse
   __syncthreads();  // every wave is done reading the ring before the epilogue reuses LDS
   if (parts > 1 && !splitk_gather<MI, NI, NT>(p, acc, smem, tile, part, parts, tid)) return;
-  igemm_epilogue<WM, WN, TM, TN, BNB, true>(p, acc, smem, tm, m0, n0, wm, wn, lane, tid, pre, early,
-                                            BNB ? smem + PARAM_OFF : nullptr);
+  igemm_epilogue<WM, WN, TM, TN, BNB, true, INF>(p, acc, smem, tm, m0, n0, wm, wn, lane, tid, pre, early,
+                                                 BNB || INF ? smem + PARAM_OFF : nullptr);
 }
 
 template <typename K>
@@ -301,6 +305,50 @@ static void launch_p3(const ConvParams& p, hipStream_t st) {
 //   32-deep, two per CU:     14 128x64 (2x2 of 64x32, 2 slots), 15 64x128 (2x2 of 32x64, 2 slots),
 //                            16 64x64 (2x2 of 32x32, 3 slots)
 //   32-deep, three per CU:   17 64x64 (2x2 of 32x32, 2 slots)
+// the inference-epilogue instantiation of a tile (forward problems only: no lhs dilation)
+template <int WM, int WN, int TM, int TN, int KW, int NST, int OCC = 1>
+static void launch_p3_inf(const ConvParams& p, hipStream_t st) {
+  constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64;
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
+  const size_t lds = p3_param_off<BM, BN, WM, KW, NST>() + inf_param_lds(BN);
+  static bool once = false;
+  if (!once) {
+    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, false, false, OCC, true>);
+    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, false, false, OCC, true>);
+    once = true;
+  }
+  if ((p.C % 64) == 0)
+    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, false, false, OCC, true>), dim3(tiles),
+                       dim3(NT), lds, st, p);
+  else
+    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, false, false, OCC, true>), dim3(tiles),
+                       dim3(NT), lds, st, p);
+}
+
+// cfg 0-17 as launch_p3_cfg below
+static void launch_p3_inf_cfg(const ConvParams& p, int cfg, hipStream_t st) {
+  switch (cfg) {
+    case 1: launch_p3_inf<2, 2, 32, 64, 64, 2, 1>(p, st); break;
+    case 2: launch_p3_inf<4, 2, 32, 32, 64, 2, 1>(p, st); break;
+    case 3: launch_p3_inf<2, 4, 32, 32, 64, 2, 1>(p, st); break;
+    case 4: launch_p3_inf<2, 2, 32, 32, 64, 2, 1>(p, st); break;
+    case 5: launch_p3_inf<4, 1, 32, 64, 64, 2, 1>(p, st); break;
+    case 6: launch_p3_inf<1, 4, 64, 32, 64, 2, 1>(p, st); break;
+    case 7: launch_p3_inf<2, 4, 64, 32, 32, 3, 1>(p, st); break;
+    case 8: launch_p3_inf<4, 2, 32, 64, 32, 3, 1>(p, st); break;
+    case 9: launch_p3_inf<2, 2, 64, 64, 32, 3, 1>(p, st); break;
+    case 10: launch_p3_inf<4, 2, 64, 64, 32, 2, 1>(p, st); break;
+    case 11: launch_p3_inf<2, 4, 64, 64, 32, 2, 1>(p, st); break;
+    case 12: launch_p3_inf<2, 2, 32, 64, 32, 4, 1>(p, st); break;
+    case 13: launch_p3_inf<2, 2, 64, 32, 32, 4, 1>(p, st); break;
+    case 14: launch_p3_inf<2, 2, 64, 32, 32, 2, 2>(p, st); break;
+    case 15: launch_p3_inf<2, 2, 32, 64, 32, 2, 2>(p, st); break;
+    case 16: launch_p3_inf<2, 2, 32, 32, 32, 3, 2>(p, st); break;
+    case 17: launch_p3_inf<2, 2, 32, 32, 32, 2, 3>(p, st); break;
+    default: launch_p3_inf<2, 2, 64, 32, 64, 2, 1>(p, st); break;
+  }
+}
+
 template <bool BNB>
 static void launch_p3_cfg(const ConvParams& p, int cfg, hipStream_t st) {
   switch (cfg) {

@@ -1,7 +1,9 @@
 // Shared epilogue of the implicit-GEMM conv kernels: fp32 accumulators -> (fused BN
 // statistics from registers) -> LDS staging (padded fp32 rows) -> coalesced 16-byte stores
 // with optional beta-accumulate, bias, fp32 output, strided-output pixel remap, and the
-// fused BN-backward gating / reduction of a data-grad GEMM (ConvParams::bnb_*).
+// fused BN-backward gating / reduction of a data-grad GEMM (ConvParams::bnb_*), or -- the INF
+// instantiations, forward-only -- the inference BN affine step, residual add and ReLU with 16-bit,
+// fp32 or plane output (ConvParams::inf).
 //
 // The fused BN-backward variant (BNB, its own kernel instantiation so the plain kernels keep
 // their register budget) fetches z / y / the beta source of a chunk of up to 4 output
@@ -134,6 +136,24 @@ __device__ __forceinline__ void stage_bnb_params(const ConvParams& p, int n0, ch
   }
 }
 
+// Inference epilogue (INF, its own kernel instantiation like BNB): the tile's per-column
+// (scale, shift) = (gamma / sqrt(var + eps), beta - mean * scale), derived at kernel start from the
+// LIVE parameter vectors (nothing comes from the host, so a graph replay sees moving statistics
+// that changed since capture) and staged in LDS where stage_bnb_params puts its table.
+constexpr size_t inf_param_lds(int BN) { return (size_t)BN * 8; }
+__device__ __forceinline__ float2 inf_coeff(const ConvParams& p, int c) {
+  const float sc = p.bnb_gamma[c] * (1.f / sqrtf(p.bnb_invstd[c] + p.inf_eps));  // bnb_invstd: the moving VARIANCE
+  return make_float2(sc, p.bnb_beta[c] - p.bnb_mean[c] * sc);
+}
+template <int BN, int NT>
+__device__ __forceinline__ void stage_inf_params(const ConvParams& p, int n0, char* base) {
+  float2* ip = reinterpret_cast<float2*>(base);
+  for (int c = threadIdx.x; c < BN; c += NT) {
+    const int gc = n0 + c;
+    ip[c] = gc < p.Nout ? inf_coeff(p, gc) : make_float2(0.f, 0.f);
+  }
+}
+
 // In-launch split-K hand-off (cdna guide Guideline 16, counter form), shared by the LDS-DMA
 // kernels: every split parks its partial tile in a workspace slab, publishes it with one
 // agent-scope release + ticket; the last arriver acquires and sums ALL slabs in index order into
@@ -183,7 +203,7 @@ __device__ __forceinline__ bool splitk_gather(const ConvParams& p, f32x4 (&acc)[
   return true;
 }
 
-template <int WM, int WN, int TM, int TN, bool BNB, bool F32 = false>
+template <int WM, int WN, int TM, int TN, bool BNB, bool F32 = false, bool INF = false>
 __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, f32x4 (&acc)[TM / 16][TN / 16], char* smem,
                                                int tm, int m0, int n0, int wm, int wn, int lane, int tid,
                                                EpiPrefetch<WM, WN, TM, TN, BNB, F32>& pre, bool prefetched,
@@ -198,11 +218,12 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, f32x4 (&acc)
   const int frow = lane & 15, fq = lane >> 4;
   float* Cs = reinterpret_cast<float*>(smem);
   constexpr int LDC16 = BN + 8;  // 16-bit staging row (16-byte aligned rows)
-  const bool s16 = !BNB && igemm_stage16(p);
+  static_assert(!(BNB && INF), "one fused epilogue per instantiation");
+  const bool s16 = !BNB && !INF && igemm_stage16(p);
   uint16_t* Cs16 = reinterpret_cast<uint16_t*>(smem);
   float* red = s16 ? reinterpret_cast<float*>(smem + (size_t)BM * LDC16 * 2)
                    : Cs + BM * LDC;  // [WM][2][BN] per-wave column partial sums
-  if (p.stats != nullptr) {
+  if (!INF && p.stats != nullptr) {
     // per-column partial BN statistics straight from the accumulators, shifted by the
     // column's K: sum the wave's row quads in registers, then across the 4 lane groups that
     // share a column with two xor-shuffles. Rows at or beyond M (only in the last row tile)
@@ -284,7 +305,7 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, f32x4 (&acc)
   }
   __syncthreads();
 
-  if (p.stats != nullptr) {
+  if (!INF && p.stats != nullptr) {
     for (int c = tid; c < BN; c += NT) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -316,7 +337,65 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, f32x4 (&acc)
     }
   };
 
-  if constexpr (!BNB) {
+  if constexpr (INF) {
+    // inference BN: v = act(v * scale + shift [+ residual]); the residual is in the output's format
+    // at the output's row and ldy; output 16-bit, fp32, or (F32, p.y_p3) planes. No stats / bias /
+    // remap-2 fill (checked on the host).
+    float isc[8], ish[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float2 q;
+      if (bnb_params != nullptr)
+        q = reinterpret_cast<const float2*>(bnb_params)[cs * 8 + e];  // zeros past Nout
+      else  // the LDS budget had no room (deepest rings): global loads
+        q = col + e < p.Nout ? inf_coeff(p, col + e) : make_float2(0.f, 0.f);
+      isc[e] = q.x;
+      ish[e] = q.y;
+    }
+    for (int it = 0; it < ITER; ++it) {
+      const int row = (tid + it * NT) / SEGS;
+      const int m = m0 + row;
+      if (!col_ok || m >= p.M) continue;
+      const size_t o = out_row(m) * p.ldy + col;
+      float v[8];
+      stage_row(row, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(v[e], isc[e], ish[e]);
+      if (p.beta) {
+        float r[8];
+        if (F32 && p.y_p3) {
+          const uint16_t* ri = reinterpret_cast<const uint16_t*>(p.yres) + o;
+          merge_p3(*reinterpret_cast<const u32x4*>(ri), *reinterpret_cast<const u32x4*>(ri + p.yres_plane),
+                   *reinterpret_cast<const u32x4*>(ri + 2 * p.yres_plane), r);
+        } else if (p.out_f32) {
+          const f32x4* ri = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.yres) + o);
+          const f32x4 r0 = ri[0], r1 = ri[1];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            r[e] = r0[e];
+            r[4 + e] = r1[e];
+          }
+        } else {
+          unpack8(*reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(p.yres) + o), r);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += r[e];
+      }
+      if (p.relu) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
+      if (F32 && p.y_p3) {
+        store_p3(reinterpret_cast<uint16_t*>(p.y) + o, p.y_plane, v);
+      } else if (p.out_f32) {
+        f32x4* yo = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + o);
+        yo[0] = f32x4{v[0], v[1], v[2], v[3]};
+        yo[1] = f32x4{v[4], v[5], v[6], v[7]};
+      } else {
+        *reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(p.y) + o) = pack8(v);
+      }
+    }
+  } else if constexpr (!BNB) {
     if (s16) {  // bf16 output, no beta / bias: rows of 8 staged 16-bit values, optional ReLU
       for (int it = 0; it < ITER; ++it) {
         const int row = (tid + it * NT) / SEGS;

@@ -82,6 +82,15 @@ struct ConvParams {
   FastDiv fd_hw, fd_w, fd_hw2, fd_w2;
   // bf16-plane operands (conv_p3.hip): x is three bf16 planes x_plane bytes apart, each x_bytes long
   uint32_t x_plane;
+  // Inference epilogue (forward-only; the INF instantiations, igemm_epilogue.h): y = act(scale * acc +
+  // shift [+ yres]) with scale = gamma / sqrt(var + inf_eps), shift = beta - mean * scale derived in
+  // the kernel from the live vectors bnb_gamma, bnb_beta, bnb_mean and bnb_invstd (here the moving
+  // VARIANCE). beta: yres is the residual, in y's format with y's rows and ldy. y_p3 (plane GEMMs):
+  // y / yres are bf16 hi / mid / lo planes y_plane / yres_plane elements apart.
+  int inf;
+  float inf_eps;
+  int y_p3;
+  int64_t y_plane, yres_plane;
 };
 void launch_conv_igemm(const ConvParams& p, int cfg, hipStream_t st);
 // cfg >= CONV_PATCH_CFG0: the 3x3 / stride 1 / pad 1 kernels with the input patch resident in
