@@ -181,7 +181,7 @@ hcb::ConvParams conv_params(const Tensor& x, const Tensor& w, const Tensor& y, c
   p.w_bytes = (uint32_t)wb;
   TORCH_CHECK(p.splits >= 1 && p.splits <= p.Kpad / 64, "hcb.conv_igemm: 1 <= splits <= k-steps");
   if (p.splits > 1) {
-    TORCH_CHECK(cfg >= 4, "hcb.conv_igemm: split-K needs an LDS-DMA config (cfg >= 4)");
+    TORCH_CHECK(hcb::conv_cfg_splitk((int)cfg), "hcb.conv_igemm: split-K needs an LDS-DMA config (cfg >= 4)");
     TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.conv_igemm: split-K workspace not set");
     const int bm = hcb::conv_tile_m((int)cfg), bn = hcb::conv_tile_n((int)cfg);
     const int64_t tiles = (int64_t)((p.M + bm - 1) / bm) * ((p.Nout + bn - 1) / bn);
@@ -316,7 +316,7 @@ void set_inf(hcb::ConvParams& p, const Tensor& y, const Tensor& gamma, const Ten
 void conv_igemm_inf(const Tensor& x, const Tensor& w, const Tensor& y, const c10::optional<Tensor>& res,
                     at::IntArrayRef g, int64_t cfg, const Tensor& gamma, const Tensor& beta, const Tensor& mean,
                     const Tensor& var, double eps) {
-  TORCH_CHECK(cfg >= 0 && cfg <= 16, "hcb.conv_igemm_inf: cfg 0..16 (a patch cfg runs its LDS-DMA twin)");
+  TORCH_CHECK(hcb::conv_cfg_has_inf((int)cfg), "hcb.conv_igemm_inf: cfg 0..16 (a patch cfg runs its LDS-DMA twin)");
   hcb::ConvParams p = conv_params(x, w, y, res, c10::nullopt, c10::nullopt, g, cfg);
   TORCH_CHECK(x.scalar_type() != at::kFloat && !p.out_f32,
               "hcb.conv_igemm_inf: 16-bit operands and output (fp32 runs on the plane GEMMs: hcb.conv_p3_inf)");
@@ -329,6 +329,31 @@ void conv_igemm_inf(const Tensor& x, const Tensor& w, const Tensor& y, const c10
 int64_t conv_tiles_m(int64_t M, int64_t cfg) {
   int t = hcb::conv_tile_m((int)cfg);
   return (M + t - 1) / t;
+}
+
+// the rows of a family's table (gemm_cfg.h), flat, 12 per cfg: cfg, kind, WM, WN, TM, TN, slot depth,
+// ring slots, occupancy, PMAX / KS, fallback cfg (-1 none), has an inference-epilogue instantiation
+std::vector<int64_t> gemm_cfg_table(std::string family) {
+  const hcb::GemmCfg* rows = nullptr;
+  int n = 0;
+  bool (*inf)(int) = [](int) { return false; };
+  if (family == "conv") {
+    rows = hcb::CONV_CFGS, n = hcb::N_CONV_CFG, inf = hcb::conv_cfg_has_inf;
+  } else if (family == "wgrad") {
+    rows = hcb::WGRAD_CFGS, n = hcb::N_WGRAD_CFG;
+  } else if (family == "p3") {
+    rows = hcb::P3_CFGS, n = hcb::N_P3_CFG, inf = hcb::p3_cfg_has_inf;
+  } else if (family == "wgrad_p3") {
+    rows = hcb::WP3_CFGS, n = hcb::N_WP3_CFG;
+  } else {
+    TORCH_CHECK(false, "hcb.gemm_cfg_table: family is conv, wgrad, p3 or wgrad_p3");
+  }
+  std::vector<int64_t> out;
+  for (int i = 0; i < n; ++i) {
+    const hcb::GemmCfg& r = rows[i];
+    for (int v : {r.cfg, r.kind, r.wm, r.wn, r.tm, r.tn, r.kw, r.nst, r.occ, r.extra, r.fb, (int)inf(i)}) out.push_back(v);
+  }
+  return out;
 }
 
 // geom = [N,H,W,C,ldx, P,Q,R,S, sh,sw,ph,pw,dh,dw, Nout,ldy]
@@ -1120,7 +1145,7 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
                           const c10::optional<Tensor>& stats, at::IntArrayRef g, int64_t cfg,
                           const c10::optional<Tensor>& stats_shift, bool y_planes = false) {
   const int64_t xps = check_planes(x, "x");
-  TORCH_CHECK(cfg >= 0 && cfg < 37, "hcb.conv_p3: cfg 0..36");
+  TORCH_CHECK(cfg >= 0 && cfg < hcb::N_P3_CFG, "hcb.conv_p3: cfg 0..36");
   // conv_params validates geometry and byte ranges on plane 0 (a bf16 tensor of this build's type);
   // split-K is validated here against the p3 tiles
   std::vector<int64_t> g1(g.begin(), g.end());
@@ -1161,7 +1186,7 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
     p.ws = g_splitk_ws;
     p.cnt = g_splitk_cnt;
   }
-  if (cfg >= 23 && cfg <= 30) {  // stream-K (conv_p3_persist.h): the launcher sizes its shares against the workspace
+  if (hcb::p3_cfg_streamk((int)cfg)) {  // stream-K (conv_p3_persist.h): the launcher sizes its shares against the workspace
     TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.conv_p3: stream-K needs the split-K workspace");
     p.ws = g_splitk_ws;
     p.cnt = g_splitk_cnt;
@@ -1195,7 +1220,7 @@ void conv_p3_bnb(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Ten
 void conv_p3_inf(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Tensor& y,
                  const c10::optional<Tensor>& res, at::IntArrayRef g, int64_t cfg, const Tensor& gamma,
                  const Tensor& beta, const Tensor& mean, const Tensor& var, double eps) {
-  TORCH_CHECK(cfg >= 0 && cfg <= 17, "hcb.conv_p3_inf: cfg 0..17 (a persistent cfg runs its per-tile twin)");
+  TORCH_CHECK(hcb::p3_cfg_has_inf((int)cfg), "hcb.conv_p3_inf: cfg 0..17 (a persistent cfg runs its per-tile twin)");
   TORCH_CHECK(g.size() >= 28, "hcb.conv_p3_inf: geom");
   const bool yp3 = y.scalar_type() == at::kBFloat16;
   TORCH_CHECK(yp3 == (g[27] == 0), "hcb.conv_p3_inf: geom out_f32 = 0 exactly for a plane output");
@@ -1231,7 +1256,7 @@ void conv_wgrad_p3(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntA
                    int64_t splits) {
   TORCH_CHECK(g.size() == 17, "hcb.conv_wgrad_p3: geom must have 17 entries");
   const int64_t dps = check_planes(dy, "dy"), xps = check_planes(x, "x");
-  TORCH_CHECK(cfg >= 0 && cfg < 19, "hcb.conv_wgrad_p3: cfg 0..18");
+  TORCH_CHECK(cfg >= 0 && cfg < hcb::N_WP3_CFG, "hcb.conv_wgrad_p3: cfg 0..18");
   check_f32(dw, "dw");
   hcb::WgradParams p{};
   p.N = g[0]; p.H = g[1]; p.W = g[2]; p.C = g[3]; p.ldx = g[4];
@@ -1251,7 +1276,7 @@ void conv_wgrad_p3(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntA
   check_range(x, 2 * xps * 2 + xb, "x planes");
   check_range(dy, 2 * dps * 2 + yb, "dy planes");
   check_range(dw, (int64_t)p.Nout * p.K * 4, "dw");
-  TORCH_CHECK(cfg < 16 || (int64_t)p.Nout * p.K * 4 < (1ll << 31),
+  TORCH_CHECK(!hcb::wp3_cfg_persistent((int)cfg) || (int64_t)p.Nout * p.K * 4 < (1ll << 31),
               "hcb.conv_wgrad_p3: the persistent configs address dW through a 32-bit buffer offset");
   const int nkt = (p.M + 63) / 64;
   const int per = (nkt + (int)splits - 1) / (int)splits;
@@ -1314,6 +1339,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("conv_igemm_bnb(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, int[] geom, int cfg, Tensor z, Tensor? yact, int ld, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor(b!) acc, int R, int mode) -> ()");
   m.def("conv_igemm_inf(Tensor x, Tensor w, Tensor(a!) y, Tensor? res, int[] geom, int cfg, Tensor gamma, Tensor beta, Tensor mean, Tensor var, float eps) -> ()");
   m.def("conv_tiles_m(int M, int cfg) -> int", conv_tiles_m);
+  m.def("gemm_cfg_table(str family) -> int[]", gemm_cfg_table);
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
   m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);
   m.def("conv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int[] geom, int cfg, int splits) -> ()");

@@ -26,7 +26,7 @@
 //     fused BN-backward for data gradients) as in the generic kernels.
 #include "common.h"
 #include "igemm_epilogue.h"
-#include "kernels.h"
+#include "igemm_launch.h"
 
 namespace hcb {
 
@@ -243,11 +243,6 @@ static int patch_span_bound(const ConvParams& p, int BM) {
   return BM - 1 + 2 * w + (2 * p.W + 4) * im + 2 * (p.W + 2) + 3;
 }
 
-template <typename K>
-static void set_lds_max(K kern) {
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 template <int WM, int WN, int TM, int TN, int NST, int PMAX>
 static bool launch_patch(ConvParams p, hipStream_t st) {
   constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64, RP = NT / 8;
@@ -267,8 +262,8 @@ static bool launch_patch(ConvParams p, hipStream_t st) {
   if (lds > 160 * 1024) return false;
   static bool once = false;
   if (!once) {
-    set_lds_max(conv3x3_patch_kernel<WM, WN, TM, TN, NST, PMAX, false>);
-    set_lds_max(conv3x3_patch_kernel<WM, WN, TM, TN, NST, PMAX, true>);
+    (void)set_lds_max(conv3x3_patch_kernel<WM, WN, TM, TN, NST, PMAX, false>);
+    (void)set_lds_max(conv3x3_patch_kernel<WM, WN, TM, TN, NST, PMAX, true>);
     once = true;
   }
   const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
@@ -279,18 +274,20 @@ static bool launch_patch(ConvParams p, hipStream_t st) {
   return true;
 }
 
-// cfg 17: 128x128 (2x4 waves of 64x32), 18: 256x128 (4x2 of 64x64), 19: 256x64 (4x2 of 64x32),
-// 20: 128x64 (2x2 of 64x32, 4 waves), 21: 128x128 with a 4-deep weight ring
+// the patch rows of gemm_cfg.h HCB_CONV_CFGS
+#define HCB_CASE_REG(...)
+#define HCB_CASE_GLDS(...)
+#define HCB_CASE_PATCH(C, WM, WN, TM, TN, NST, PMAX, FB) \
+  case C: return launch_patch<WM, WN, TM, TN, NST, PMAX>(p, st);
 bool launch_conv3x3_patch(const ConvParams& p, int cfg, hipStream_t st) {
   if (!conv3x3_patch_eligible(p)) return false;
   switch (cfg) {
-    case 17: return launch_patch<2, 4, 64, 32, 3, 8>(p, st);
-    case 18: return launch_patch<4, 2, 64, 64, 3, 8>(p, st);
-    case 19: return launch_patch<4, 2, 64, 32, 3, 8>(p, st);
-    case 20: return launch_patch<2, 2, 64, 32, 3, 16>(p, st);
-    case 21: return launch_patch<2, 4, 64, 32, 4, 8>(p, st);
+    HCB_CONV_CFGS(HCB_CASE)
     default: return false;
   }
 }
+#undef HCB_CASE_REG
+#undef HCB_CASE_GLDS
+#undef HCB_CASE_PATCH
 
 }  // namespace hcb

@@ -33,8 +33,8 @@
 //     fp32 output, strided-output remap.
 #include "common.h"
 #include "igemm_epilogue.h"
+#include "igemm_launch.h"
 #include "igemm_loader.h"
-#include "kernels.h"
 
 namespace hcb {
 
@@ -299,207 +299,82 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void conv_igemm_glds_ker
 }
 
 // ============================================================== launch
-// One instantiation per (im2col path, lhs-dilation, fused BN-backward epilogue); the BNB
-// variants are separate kernels so the plain ones keep their register budget.
-template <typename K>
-static void set_lds_once(K kern) {
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-template <int WM, int WN, int TM, int TN, bool BNB>
+// One instantiation per (im2col path, lhs-dilation, epilogue): the fused BN-backward (BNB) and the
+// inference (INF) variants are separate kernels so the plain ones keep their register budget.
+template <int WM, int WN, int TM, int TN, bool BNB, bool INF>
 static void launch_reg(const ConvParams& p, hipStream_t st) {
   constexpr int BM = WM * TM, BN = WN * TN;
-  int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN);
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN);
   // a single k-step (1x1 over <= 64 channels) uses one buffer pair
-  size_t lds_main = (size_t)(p.Kpad > 64 ? 2 : 1) * (BM + BN) * 8 * 16;
-  size_t lds_epi = igemm_epilogue_lds(BM, BN, WM, igemm_stage16(p));
+  const size_t lds_main = (size_t)(p.Kpad > 64 ? 2 : 1) * (BM + BN) * 8 * 16;
+  const size_t lds_epi = igemm_epilogue_lds(BM, BN, WM, igemm_stage16(p));
   size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   if (BNB) lds = reg_param_off(BM, BN, WM) + bnb_param_lds(BN);
-  bool cbig = (p.C % 64) == 0;
-  bool lhs = p.idil_h > 1 || p.idil_w > 1;
-  static bool once = false;
-  if (!once) {
-    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, true, false, BNB>);
-    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, true, true, BNB>);
-    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, false, false, BNB>);
-    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, false, true, BNB>);
-    once = true;
-  }
-  if (cbig && !lhs)
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false, BNB>), dim3(tiles), dim3(256), lds, st, p);
-  else if (cbig && lhs)
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, true, BNB>), dim3(tiles), dim3(256), lds, st, p);
-  else if (!cbig && !lhs)
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false, BNB>), dim3(tiles), dim3(256), lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, true, BNB>), dim3(tiles), dim3(256), lds, st, p);
+  if (INF) lds = reg_param_off(BM, BN, WM) + inf_param_lds(BN);
+  launch_igemm<INF>(
+      [](auto cbig, auto lhs) {
+        return conv_igemm_kernel<WM, WN, TM, TN, decltype(cbig)::value, decltype(lhs)::value, BNB, INF>;
+      },
+      tiles, 256, lds, st, p);
 }
 
-template <int WM, int WN, int TM, int TN, int NST, bool BNB>
+template <int WM, int WN, int TM, int TN, int NST, bool BNB, bool INF>
 static void launch_glds(const ConvParams& p, hipStream_t st) {
   constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64;
-  int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
   // a block never touches more ring stages than it has k-steps (short-K layers: 1x1 over 64-256
   // channels, 1-4 k-steps, get the LDS they use, so more workgroups fit per CU)
   const int ksteps = (p.Kpad / 64 + p.splits - 1) / p.splits;
   const int stages = ksteps < NST ? (ksteps > 0 ? ksteps : 1) : NST;
-  size_t lds_main = (size_t)stages * (BM + BN) * 128;
-  size_t lds_epi = igemm_epilogue_lds(BM, BN, WM, igemm_stage16(p));
+  const size_t lds_main = (size_t)stages * (BM + BN) * 128;
+  const size_t lds_epi = igemm_epilogue_lds(BM, BN, WM, igemm_stage16(p));
   size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  if (BNB && glds_param_off(BM, BN, WM, NST) + bnb_param_lds(BN) <= 160 * 1024)
-    lds = glds_param_off(BM, BN, WM, NST) + bnb_param_lds(BN);
-  bool cbig = (p.C % 64) == 0;
-  bool lhs = p.idil_h > 1 || p.idil_w > 1;
-  static bool once = false;
-  if (!once) {
-    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, false, BNB>);
-    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, true, BNB>);
-    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, false, BNB>);
-    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, true, BNB>);
-    once = true;
-  }
-  if (cbig && !lhs)
-    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, false, BNB>), dim3(tiles), dim3(NT), lds, st, p);
-  else if (cbig && lhs)
-    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, true, BNB>), dim3(tiles), dim3(NT), lds, st, p);
-  else if (!cbig && !lhs)
-    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, false, BNB>), dim3(tiles), dim3(NT), lds, st,
-                       p);
-  else
-    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, true, BNB>), dim3(tiles), dim3(NT), lds, st, p);
-}
-
-// The inference-epilogue instantiations (forward problems only: no lhs dilation). Their LDS is the
-// ring / staging extent plus the (scale, shift) table; a ring that fills LDS (cfg 9) loads the
-// coefficients from global memory instead.
-template <int WM, int WN, int TM, int TN>
-static void launch_reg_inf(const ConvParams& p, hipStream_t st) {
-  constexpr int BM = WM * TM, BN = WN * TN;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN);
-  const size_t lds = reg_param_off(BM, BN, WM) + inf_param_lds(BN);
-  static bool once = false;
-  if (!once) {
-    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, true, false, false, true>);
-    set_lds_once(conv_igemm_kernel<WM, WN, TM, TN, false, false, false, true>);
-    once = true;
-  }
-  if ((p.C % 64) == 0)
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false, false, true>), dim3(tiles), dim3(256), lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false, false, true>), dim3(tiles), dim3(256), lds, st, p);
-}
-
-template <int WM, int WN, int TM, int TN, int NST>
-static void launch_glds_inf(const ConvParams& p, hipStream_t st) {
-  constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
+  // the epilogue's parameter table sits above the full ring; a ring that fills LDS (cfg 9) loads
+  // the coefficients from global memory instead (the INF form then keeps the untrimmed extent)
   constexpr size_t OFF = glds_param_off(BM, BN, WM, NST);
-  const size_t lds = OFF + inf_param_lds(BN) <= 160 * 1024 ? OFF + inf_param_lds(BN) : OFF;
-  static bool once = false;
-  if (!once) {
-    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, false, false, true>);
-    set_lds_once(conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, false, false, true>);
-    once = true;
-  }
-  if ((p.C % 64) == 0)
-    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, true, false, false, true>), dim3(tiles), dim3(NT),
-                       lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_glds_kernel<WM, WN, TM, TN, NST, false, false, false, true>), dim3(tiles), dim3(NT),
-                       lds, st, p);
+  if (BNB && OFF + bnb_param_lds(BN) <= 160 * 1024) lds = OFF + bnb_param_lds(BN);
+  if (INF) lds = OFF + inf_param_lds(BN) <= 160 * 1024 ? OFF + inf_param_lds(BN) : OFF;
+  launch_igemm<INF>(
+      [](auto cbig, auto lhs) {
+        return conv_igemm_glds_kernel<WM, WN, TM, TN, NST, decltype(cbig)::value, decltype(lhs)::value, BNB, INF>;
+      },
+      tiles, NT, lds, st, p);
 }
 
-// cfg: 0..3 register-staged {128x128, 128x64, 64x64, 64x128}; 4..7 the same tiles on the
-// LDS-DMA ring (NST 3, 3, 4, 3); 8..11 deeper rings for latency-bound few-tile layers
-// (128x128 NST 4 and 5, 128x64 NST 6, 64x128 NST 6); 12..16 eight-wave workgroups (two
-// waves per SIMD when a layer has only ~1 tile per CU): 128x128 as 2x4 waves of 64x32 and as
-// 4x2 of 32x64, 256x128 (4x2 of 64x64), 128x256 (2x4 of 64x64), 64x128 (2x4 of 32x32);
-// 17..21 the 3x3 patch kernels (conv3x3_patch.hip): 128x128, 256x128, 256x64, 128x64, 128x128;
-// (round 5: the rejected variants -- two k-steps per stage, cfg 22-26; occupancy-sized two-slot
-// rings, 27-30; the register-pipelined loop, 31-37; the plane kernel on one 16-bit plane, 100-117 --
-// were measured without a step gain and removed: profiles/r5_prune_variants.txt)
-constexpr int N_CONV_CFG = 22;
-int conv_tile_m(int cfg) {
-  static const int t[N_CONV_CFG] = {128, 128, 64, 64, 128, 128, 64, 64, 128, 128, 128,
-                                    64,  128, 128, 256, 128, 64, 128, 256, 256, 128, 128};
-  return (cfg >= 0 && cfg < N_CONV_CFG) ? t[cfg] : 128;
-}
-int conv_tile_n(int cfg) {
-  static const int t[N_CONV_CFG] = {128, 64,  64,  128, 128, 64,  64, 128, 128, 128, 64,
-                                    128, 128, 128, 128, 256, 128, 128, 128, 64, 64, 128};
-  return (cfg >= 0 && cfg < N_CONV_CFG) ? t[cfg] : 128;
-}
-
-template <bool BNB>
+// the rows of gemm_cfg.h HCB_CONV_CFGS; a cfg without a kernel here (a patch row, a number outside
+// the table) runs cfg 0
+#define HCB_CASE_REG(C, WM, WN, TM, TN, NST, PMAX, FB) \
+  case C: launch_reg<WM, WN, TM, TN, BNB, INF>(p, st); break;
+#define HCB_CASE_GLDS(C, WM, WN, TM, TN, NST, PMAX, FB) \
+  case C: launch_glds<WM, WN, TM, TN, NST, BNB, INF>(p, st); break;
+#define HCB_CASE_PATCH(C, WM, WN, TM, TN, NST, PMAX, FB)
+template <bool BNB, bool INF>
 static void launch_cfg(const ConvParams& p, int cfg, hipStream_t st) {
   switch (cfg) {
-    case 0: launch_reg<2, 2, 64, 64, BNB>(p, st); break;    // 128 x 128
-    case 1: launch_reg<4, 1, 32, 64, BNB>(p, st); break;    // 128 x 64
-    case 2: launch_reg<2, 2, 32, 32, BNB>(p, st); break;    // 64 x 64
-    case 3: launch_reg<1, 4, 64, 32, BNB>(p, st); break;    // 64 x 128
-    case 4: launch_glds<2, 2, 64, 64, 3, BNB>(p, st); break;
-    case 5: launch_glds<4, 1, 32, 64, 3, BNB>(p, st); break;
-    case 6: launch_glds<2, 2, 32, 32, 4, BNB>(p, st); break;
-    case 7: launch_glds<1, 4, 64, 32, 3, BNB>(p, st); break;
-    case 8: launch_glds<2, 2, 64, 64, 4, BNB>(p, st); break;
-    case 9: launch_glds<2, 2, 64, 64, 5, BNB>(p, st); break;
-    case 10: launch_glds<4, 1, 32, 64, 6, BNB>(p, st); break;
-    case 11: launch_glds<1, 4, 64, 32, 6, BNB>(p, st); break;
-    case 12: launch_glds<2, 4, 64, 32, 3, BNB>(p, st); break;
-    case 13: launch_glds<4, 2, 32, 64, 3, BNB>(p, st); break;
-    case 14: launch_glds<4, 2, 64, 64, 3, BNB>(p, st); break;
-    case 15: launch_glds<2, 4, 64, 64, 3, BNB>(p, st); break;
-    case 16: launch_glds<2, 4, 32, 32, 4, BNB>(p, st); break;
-    default: launch_reg<2, 2, 64, 64, BNB>(p, st); break;
+    HCB_CONV_CFGS(HCB_CASE)
+    default: launch_cfg<BNB, INF>(p, 0, st); break;
   }
 }
-
-// cfg 0-16 as launch_cfg
-static void launch_inf_cfg(const ConvParams& p, int cfg, hipStream_t st) {
-  switch (cfg) {
-    case 1: launch_reg_inf<4, 1, 32, 64>(p, st); break;
-    case 2: launch_reg_inf<2, 2, 32, 32>(p, st); break;
-    case 3: launch_reg_inf<1, 4, 64, 32>(p, st); break;
-    case 4: launch_glds_inf<2, 2, 64, 64, 3>(p, st); break;
-    case 5: launch_glds_inf<4, 1, 32, 64, 3>(p, st); break;
-    case 6: launch_glds_inf<2, 2, 32, 32, 4>(p, st); break;
-    case 7: launch_glds_inf<1, 4, 64, 32, 3>(p, st); break;
-    case 8: launch_glds_inf<2, 2, 64, 64, 4>(p, st); break;
-    case 9: launch_glds_inf<2, 2, 64, 64, 5>(p, st); break;
-    case 10: launch_glds_inf<4, 1, 32, 64, 6>(p, st); break;
-    case 11: launch_glds_inf<1, 4, 64, 32, 6>(p, st); break;
-    case 12: launch_glds_inf<2, 4, 64, 32, 3>(p, st); break;
-    case 13: launch_glds_inf<4, 2, 32, 64, 3>(p, st); break;
-    case 14: launch_glds_inf<4, 2, 64, 64, 3>(p, st); break;
-    case 15: launch_glds_inf<2, 4, 64, 64, 3>(p, st); break;
-    case 16: launch_glds_inf<2, 4, 32, 32, 4>(p, st); break;
-    default: launch_reg_inf<2, 2, 64, 64>(p, st); break;
-  }
-}
+#undef HCB_CASE_REG
+#undef HCB_CASE_GLDS
+#undef HCB_CASE_PATCH
 
 void launch_conv_igemm(const ConvParams& p, int cfg, hipStream_t st) {
-  if (p.inf) {  // the inference epilogue: cfg 0-16 (checked by the binding; no patch kernels)
-    launch_inf_cfg(p, cfg, st);
+  if (p.inf) {  // the inference epilogue (the binding admits the cfgs that have one: no patch kernels)
+    launch_cfg<false, true>(p, cfg, st);
     return;
   }
-  if (cfg >= CONV_PATCH_CFG0 && cfg < CONV_PATCH_CFG0 + 5) {
+  ConvParams q = p;
+  if (gemm_kind(CONV_CFGS, cfg) == K_PATCH) {
     if (launch_conv3x3_patch(p, cfg, st)) return;
-    // not a 3x3 / stride-1 problem (or its patch does not fit LDS): an LDS-DMA kernel of the
-    // same row tile (so per-tile statistics slabs keep their size), without split-K
-    static const int fallback[5] = {13, 14, 14, 5, 13};
-    ConvParams q = p;
+    // not a 3x3 / stride-1 problem (or its patch does not fit LDS): the row's fallback, without split-K
     q.splits = 1;
-    cfg = fallback[cfg - CONV_PATCH_CFG0];
-    if (q.bnb_acc != nullptr)
-      launch_cfg<true>(q, cfg, st);
-    else
-      launch_cfg<false>(q, cfg, st);
-    return;
+    cfg = CONV_CFGS[cfg].fb;
   }
-  if (p.bnb_acc != nullptr)
-    launch_cfg<true>(p, cfg, st);
+  if (q.bnb_acc != nullptr)
+    launch_cfg<true, false>(q, cfg, st);
   else
-    launch_cfg<false>(p, cfg, st);
+    launch_cfg<false, false>(q, cfg, st);
 }
 
 }  // namespace hcb

@@ -24,110 +24,57 @@
 
 namespace hcb {
 
-// cfg 0-17: conv_igemm_p3_kernel (conv_p3_fwd.h); 18-22: the persistent short-K kernel
-// (conv_p3_persist.h), twins of 15, 14, 16, 17 and 7; 23-27: its stream-K form (tiles of 18-22);
-// 28: stream-K with cfg 8's geometry (4 x 2 waves of 32 x 64); 29 / 30 (stream-K 256 x 128 / 128 x 256
-// of 64 x 64 wave tiles) are retired -- a 272-byte stack frame, 5x slower (profiles/r6_quantization_streamk.txt)
-// -- and launch cfg 10 / 11
-// 31-36: the persistent kernel with the workgroup's weight slice resident in LDS (BRES): 64x256 (4
-// waves of 64x64), 128x256 (8 waves of 64x64), 64x64 (4 waves of 32x32), 128x64 (4 waves of 64x32),
-// 128x64 (8 waves of 32x32), 128x128 (8 waves of 32x64)
-constexpr int N_P3_CFG = 37;
-int p3_tile_m(int cfg) {
-  static const int t[N_P3_CFG] = {128, 64, 128, 64, 64, 128, 64, 128, 128, 128, 256, 128, 64, 128, 128, 64,
-                                  64, 64, 64, 128, 64, 64, 128, 64, 128, 64, 64, 128, 128, 256, 128,
-                                  64, 128, 64, 128, 128, 128};
-  return (cfg >= 0 && cfg < N_P3_CFG) ? t[cfg] : 128;
-}
-int p3_slot_k(int cfg) { return (cfg >= 0 && cfg <= 6) ? 64 : 32; }
-int p3_tile_n(int cfg) {
-  static const int t[N_P3_CFG] = {64, 128, 64, 128, 64, 64, 128, 128, 128, 128, 128, 256, 128, 64, 64, 128,
-                                  64, 64, 128, 64, 64, 64, 128, 128, 64, 64, 64, 128, 128, 128, 256,
-                                  256, 256, 64, 64, 64, 128};
-  return (cfg >= 0 && cfg < N_P3_CFG) ? t[cfg] : 64;
-}
-
-// the persistent cfg, or (a problem with an epilogue it does not serve) its twin; the stream-K cfg,
-// else its whole-tile persistent form
+// The rows of gemm_cfg.h HCB_P3_CFGS beyond the per-tile kernels: the persistent, stream-K and
+// weights-resident launchers return false for a problem they do not serve (an epilogue, a shape);
+// the row's fallback then runs, down to a per-tile cfg, which is returned. -1: launched.
+#define HCB_CASE_TILE(...)
+#define HCB_CASE_PERSIST(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
+  case C: return launch_p3p<WM, WN, TM, TN, KW, NST, OCC>(p, st) ? -1 : launch_p3_persist(p, FB, st);
+#define HCB_CASE_STREAMK(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
+  case C: return launch_p3sk<WM, WN, TM, TN, KW, NST, OCC>(p, st) ? -1 : launch_p3_persist(p, FB, st);
+#define HCB_CASE_BRES(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
+  case C: return launch_p3bres<WM, WN, TM, TN, KW, NST>(p, st) ? -1 : launch_p3_persist(p, FB, st);
+#define HCB_CASE_RETIRED(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
+  case C: return launch_p3_persist(p, FB, st);
 static int launch_p3_persist(const ConvParams& p, int cfg, hipStream_t st) {
   switch (cfg) {
-    case 23: return launch_p3sk<2, 2, 32, 64, 32, 2, 2>(p, st) ? -1 : launch_p3_persist(p, 18, st);
-    case 24: return launch_p3sk<2, 2, 64, 32, 32, 2, 2>(p, st) ? -1 : launch_p3_persist(p, 19, st);
-    case 25: return launch_p3sk<2, 2, 32, 32, 32, 3, 2>(p, st) ? -1 : launch_p3_persist(p, 20, st);
-    case 26: return launch_p3sk<2, 2, 32, 32, 32, 2, 3>(p, st) ? -1 : launch_p3_persist(p, 21, st);
-    case 27: return launch_p3sk<2, 4, 64, 32, 32, 3, 1>(p, st) ? -1 : launch_p3_persist(p, 22, st);
-    case 28: return launch_p3sk<4, 2, 32, 64, 32, 3, 1>(p, st) ? -1 : 8;
-    case 29: return 10;
-    case 30: return 11;
-    case 31: return launch_p3bres<1, 4, 64, 64, 32, 3>(p, st) ? -1 : launch_p3_persist(p, 18, st);
-    case 32: return launch_p3bres<2, 4, 64, 64, 32, 2>(p, st) ? -1 : launch_p3_persist(p, 18, st);
-    case 33: return launch_p3bres<2, 2, 32, 32, 32, 3>(p, st) ? -1 : launch_p3_persist(p, 20, st);
-    case 34: return launch_p3bres<2, 2, 64, 32, 32, 2>(p, st) ? -1 : launch_p3_persist(p, 19, st);
-    case 35: return launch_p3bres<4, 2, 32, 32, 32, 2>(p, st) ? -1 : launch_p3_persist(p, 19, st);
-    case 36: return launch_p3bres<4, 2, 32, 64, 32, 2>(p, st) ? -1 : launch_p3_persist(p, 22, st);
-    case 18: return launch_p3p<2, 2, 32, 64, 32, 2, 2>(p, st) ? -1 : 15;
-    case 19: return launch_p3p<2, 2, 64, 32, 32, 2, 2>(p, st) ? -1 : 14;
-    case 20: return launch_p3p<2, 2, 32, 32, 32, 3, 2>(p, st) ? -1 : 16;
-    case 21: return launch_p3p<2, 2, 32, 32, 32, 2, 3>(p, st) ? -1 : 17;
-    case 22: return launch_p3p<2, 4, 64, 32, 32, 3, 1>(p, st) ? -1 : 7;
+    HCB_P3_CFGS(HCB_CASE)
     default: return cfg;
   }
 }
+#undef HCB_CASE_TILE
+#undef HCB_CASE_PERSIST
+#undef HCB_CASE_STREAMK
+#undef HCB_CASE_BRES
+#undef HCB_CASE_RETIRED
 
 void set_p3p_bnb(int v) { p3p_bnb_level() = v; }
 
 void launch_conv_p3(const ConvParams& p, int cfg, hipStream_t st) {
-  if (p.inf) {  // the inference epilogue: per-tile kernels only (cfg 0-17, checked by the binding)
-    launch_p3_inf_cfg(p, cfg, st);
+  if (p.inf) {  // the inference epilogue: per-tile kernels only (checked by the binding)
+    launch_p3_cfg<false, true>(p, cfg, st);
     return;
   }
-  if (cfg >= 18 && (cfg = launch_p3_persist(p, cfg, st)) < 0) return;
+  if (cfg >= 0 && (cfg = launch_p3_persist(p, cfg, st)) < 0) return;
   if (p.bnb_acc != nullptr)
-    launch_p3_cfg<true>(p, cfg, st);
+    launch_p3_cfg<true, false>(p, cfg, st);
   else
-    launch_p3_cfg<false>(p, cfg, st);
-}
-// p3 wgrad cfg (block tile, waves x wave tile, slots x pixel rows):
-//   0 128x64 (2x2 of 64x32, 2x64), 1 64x128 (2x2 of 32x64, 2x64), 2 64x64 (2x2 of 32x32, 3x64),
-//   3 128x64 (4x2 of 32x32, 2x64), 4 64x128 (2x4 of 32x32, 2x64), 5 64x64 (2x2 of 32x32, 2x64),
-//   6 128x128 (2x4 of 64x32, 3x32), 7 128x128 (4x2 of 32x64, 3x32), 8 256x128 (4x2 of 64x64, 2x32),
-//   9 128x256 (2x4 of 64x64, 2x32), 10 128x128 (2x2 of 64x64, 3x32), 11 128x64 (2x2 of 64x32, 3x32),
-//   two per CU: 12 128x64 (2x2 of 64x32, 2x32), 13 64x128 (2x2 of 32x64, 2x32), 14 64x64 (2x2 of 32x32, 3x32),
-//   three per CU: 15 64x64 (2x2 of 32x32, 2x32)
-//   persistent (conv_p3_persist.h, twins of 12, 13, 15): 16 128x64, 17 64x128, 18 64x64
-constexpr int N_WP3_CFG = 19;
-int wgrad_p3_tile_m(int cfg) {
-  static const int t[N_WP3_CFG] = {128, 64, 64, 128, 64, 64, 128, 128, 256, 128, 128, 128, 128, 64, 64, 64, 128, 64, 64};
-  return (cfg >= 0 && cfg < N_WP3_CFG) ? t[cfg] : 64;
-}
-int wgrad_p3_tile_n(int cfg) {
-  static const int t[N_WP3_CFG] = {64, 128, 64, 64, 128, 64, 128, 128, 128, 256, 128, 64, 64, 128, 64, 64, 64, 128, 64};
-  return (cfg >= 0 && cfg < N_WP3_CFG) ? t[cfg] : 64;
+    launch_p3_cfg<false, false>(p, cfg, st);
 }
 
+// the rows of gemm_cfg.h HCB_WP3_CFGS; a cfg outside the table runs cfg 2
+#define HCB_CASE_TILE(C, WM, WN, TM, TN, KW, NST, OCC) \
+  case C: wlaunch_p3<WM, WN, TM, TN, NST, KW, OCC>(p, splits, st); break;
+#define HCB_CASE_PERSIST(C, WM, WN, TM, TN, KW, NST, OCC) \
+  case C: wlaunch_p3p<WM, WN, TM, TN, OCC>(p, splits, st); break;
 void launch_wgrad_p3(const WgradParams& p, int cfg, int splits, hipStream_t st) {
   switch (cfg) {
-    case 16: wlaunch_p3p<2, 2, 64, 32, 2>(p, splits, st); break;
-    case 17: wlaunch_p3p<2, 2, 32, 64, 2>(p, splits, st); break;
-    case 18: wlaunch_p3p<2, 2, 32, 32, 3>(p, splits, st); break;
-    case 0: wlaunch_p3<2, 2, 64, 32, 2, 64>(p, splits, st); break;
-    case 1: wlaunch_p3<2, 2, 32, 64, 2, 64>(p, splits, st); break;
-    case 3: wlaunch_p3<4, 2, 32, 32, 2, 64>(p, splits, st); break;
-    case 4: wlaunch_p3<2, 4, 32, 32, 2, 64>(p, splits, st); break;
-    case 5: wlaunch_p3<2, 2, 32, 32, 2, 64>(p, splits, st); break;
-    case 6: wlaunch_p3<2, 4, 64, 32, 3, 32>(p, splits, st); break;
-    case 7: wlaunch_p3<4, 2, 32, 64, 3, 32>(p, splits, st); break;
-    case 8: wlaunch_p3<4, 2, 64, 64, 2, 32>(p, splits, st); break;
-    case 9: wlaunch_p3<2, 4, 64, 64, 2, 32>(p, splits, st); break;
-    case 10: wlaunch_p3<2, 2, 64, 64, 3, 32>(p, splits, st); break;
-    case 11: wlaunch_p3<2, 2, 64, 32, 3, 32>(p, splits, st); break;
-    case 12: wlaunch_p3<2, 2, 64, 32, 2, 32, 2>(p, splits, st); break;
-    case 13: wlaunch_p3<2, 2, 32, 64, 2, 32, 2>(p, splits, st); break;
-    case 14: wlaunch_p3<2, 2, 32, 32, 3, 32, 2>(p, splits, st); break;
-    case 15: wlaunch_p3<2, 2, 32, 32, 2, 32, 3>(p, splits, st); break;
-    default: wlaunch_p3<2, 2, 32, 32, 3, 64>(p, splits, st); break;
+    HCB_WP3_CFGS(HCB_CASE)
+    default: launch_wgrad_p3(p, 2, splits, st); break;
   }
 }
+#undef HCB_CASE_TILE
+#undef HCB_CASE_PERSIST
 
 // ============================================================== plane split / merge
 // x fp32 [rows][ldx] (C channels used) -> three bf16 planes [3][rows][ldo] (plane stride `plane`

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "igemm_epilogue.h"
+#include "igemm_launch.h"
 #include "igemm_loader.h"
 #include "kernels.h"
 
@@ -257,12 +258,7 @@ __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_igemm_p3_ke
                                                  BNB || INF ? smem + PARAM_OFF : nullptr);
 }
 
-template <typename K>
-static void p3_set_lds_once(K kern) {
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-template <int WM, int WN, int TM, int TN, int KW, int NST, bool BNB, int OCC = 1>
+template <int WM, int WN, int TM, int TN, int KW, int NST, int OCC, bool BNB, bool INF>
 static void launch_p3(const ConvParams& p, hipStream_t st) {
   constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64;
   const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
@@ -270,107 +266,32 @@ static void launch_p3(const ConvParams& p, hipStream_t st) {
   const size_t lds_epi = igemm_epilogue_lds(BM, BN, WM);
   size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   if (BNB) lds = p3_param_off<BM, BN, WM, KW, NST>() + bnb_param_lds(BN);
-  const bool cbig = (p.C % 64) == 0;
-  const bool lhs = p.idil_h > 1 || p.idil_w > 1;
-  static bool once = false;
-  if (!once) {
-    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, false, BNB, OCC>);
-    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, true, BNB, OCC>);
-    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, false, BNB, OCC>);
-    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, true, BNB, OCC>);
-    once = true;
-  }
-  if (cbig && !lhs)
-    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, false, BNB, OCC>), dim3(tiles), dim3(NT),
-                       lds, st, p);
-  else if (cbig && lhs)
-    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, true, BNB, OCC>), dim3(tiles), dim3(NT),
-                       lds, st, p);
-  else if (!cbig && !lhs)
-    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, false, BNB, OCC>), dim3(tiles), dim3(NT),
-                       lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, true, BNB, OCC>), dim3(tiles), dim3(NT),
-                       lds, st, p);
+  if (INF) lds = p3_param_off<BM, BN, WM, KW, NST>() + inf_param_lds(BN);
+  launch_igemm<INF>(
+      [](auto cbig, auto lhs) {
+        return conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, decltype(cbig)::value, decltype(lhs)::value, BNB, OCC, INF>;
+      },
+      tiles, NT, lds, st, p);
 }
 
-// p3 cfg (block tile, waves x wave tile, slot depth, ring slots):
-//   64-deep slots, 2 slots:  0 128x64 (2x2 of 64x32), 1 64x128 (2x2 of 32x64), 2 128x64 (4x2 of 32x32),
-//                            3 64x128 (2x4 of 32x32), 4 64x64 (2x2 of 32x32), 5 128x64 (4x1 of 32x64),
-//                            6 64x128 (1x4 of 64x32)
-//   32-deep slots:           7 128x128 (2x4 of 64x32, 3 slots), 8 128x128 (4x2 of 32x64, 3 slots),
-//                            9 128x128 (2x2 of 64x64, 3 slots), 10 256x128 (4x2 of 64x64, 2 slots),
-//                            11 128x256 (2x4 of 64x64, 2 slots), 12 64x128 (2x2 of 32x64, 4 slots),
-//                            13 128x64 (2x2 of 64x32, 4 slots)
-//   32-deep, two per CU:     14 128x64 (2x2 of 64x32, 2 slots), 15 64x128 (2x2 of 32x64, 2 slots),
-//                            16 64x64 (2x2 of 32x32, 3 slots)
-//   32-deep, three per CU:   17 64x64 (2x2 of 32x32, 2 slots)
-// the inference-epilogue instantiation of a tile (forward problems only: no lhs dilation)
-template <int WM, int WN, int TM, int TN, int KW, int NST, int OCC = 1>
-static void launch_p3_inf(const ConvParams& p, hipStream_t st) {
-  constexpr int BM = WM * TM, BN = WN * TN, NT = WM * WN * 64;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN) * p.splits;
-  const size_t lds = p3_param_off<BM, BN, WM, KW, NST>() + inf_param_lds(BN);
-  static bool once = false;
-  if (!once) {
-    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, false, false, OCC, true>);
-    p3_set_lds_once(conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, false, false, OCC, true>);
-    once = true;
-  }
-  if ((p.C % 64) == 0)
-    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, true, false, false, OCC, true>), dim3(tiles),
-                       dim3(NT), lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_p3_kernel<WM, WN, TM, TN, KW, NST, false, false, false, OCC, true>), dim3(tiles),
-                       dim3(NT), lds, st, p);
-}
-
-// cfg 0-17 as launch_p3_cfg below
-static void launch_p3_inf_cfg(const ConvParams& p, int cfg, hipStream_t st) {
-  switch (cfg) {
-    case 1: launch_p3_inf<2, 2, 32, 64, 64, 2, 1>(p, st); break;
-    case 2: launch_p3_inf<4, 2, 32, 32, 64, 2, 1>(p, st); break;
-    case 3: launch_p3_inf<2, 4, 32, 32, 64, 2, 1>(p, st); break;
-    case 4: launch_p3_inf<2, 2, 32, 32, 64, 2, 1>(p, st); break;
-    case 5: launch_p3_inf<4, 1, 32, 64, 64, 2, 1>(p, st); break;
-    case 6: launch_p3_inf<1, 4, 64, 32, 64, 2, 1>(p, st); break;
-    case 7: launch_p3_inf<2, 4, 64, 32, 32, 3, 1>(p, st); break;
-    case 8: launch_p3_inf<4, 2, 32, 64, 32, 3, 1>(p, st); break;
-    case 9: launch_p3_inf<2, 2, 64, 64, 32, 3, 1>(p, st); break;
-    case 10: launch_p3_inf<4, 2, 64, 64, 32, 2, 1>(p, st); break;
-    case 11: launch_p3_inf<2, 4, 64, 64, 32, 2, 1>(p, st); break;
-    case 12: launch_p3_inf<2, 2, 32, 64, 32, 4, 1>(p, st); break;
-    case 13: launch_p3_inf<2, 2, 64, 32, 32, 4, 1>(p, st); break;
-    case 14: launch_p3_inf<2, 2, 64, 32, 32, 2, 2>(p, st); break;
-    case 15: launch_p3_inf<2, 2, 32, 64, 32, 2, 2>(p, st); break;
-    case 16: launch_p3_inf<2, 2, 32, 32, 32, 3, 2>(p, st); break;
-    case 17: launch_p3_inf<2, 2, 32, 32, 32, 2, 3>(p, st); break;
-    default: launch_p3_inf<2, 2, 64, 32, 64, 2, 1>(p, st); break;
-  }
-}
-
-template <bool BNB>
+// the per-tile rows of gemm_cfg.h HCB_P3_CFGS; any other cfg runs cfg 0
+#define HCB_CASE_TILE(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
+  case C: launch_p3<WM, WN, TM, TN, KW, NST, OCC, BNB, INF>(p, st); break;
+#define HCB_CASE_PERSIST(...)
+#define HCB_CASE_STREAMK(...)
+#define HCB_CASE_BRES(...)
+#define HCB_CASE_RETIRED(...)
+template <bool BNB, bool INF>
 static void launch_p3_cfg(const ConvParams& p, int cfg, hipStream_t st) {
   switch (cfg) {
-    case 1: launch_p3<2, 2, 32, 64, 64, 2, BNB, 1>(p, st); break;
-    case 2: launch_p3<4, 2, 32, 32, 64, 2, BNB, 1>(p, st); break;
-    case 3: launch_p3<2, 4, 32, 32, 64, 2, BNB, 1>(p, st); break;
-    case 4: launch_p3<2, 2, 32, 32, 64, 2, BNB, 1>(p, st); break;
-    case 5: launch_p3<4, 1, 32, 64, 64, 2, BNB, 1>(p, st); break;
-    case 6: launch_p3<1, 4, 64, 32, 64, 2, BNB, 1>(p, st); break;
-    case 7: launch_p3<2, 4, 64, 32, 32, 3, BNB, 1>(p, st); break;
-    case 8: launch_p3<4, 2, 32, 64, 32, 3, BNB, 1>(p, st); break;
-    case 9: launch_p3<2, 2, 64, 64, 32, 3, BNB, 1>(p, st); break;
-    case 10: launch_p3<4, 2, 64, 64, 32, 2, BNB, 1>(p, st); break;
-    case 11: launch_p3<2, 4, 64, 64, 32, 2, BNB, 1>(p, st); break;
-    case 12: launch_p3<2, 2, 32, 64, 32, 4, BNB, 1>(p, st); break;
-    case 13: launch_p3<2, 2, 64, 32, 32, 4, BNB, 1>(p, st); break;
-    case 14: launch_p3<2, 2, 64, 32, 32, 2, BNB, 2>(p, st); break;
-    case 15: launch_p3<2, 2, 32, 64, 32, 2, BNB, 2>(p, st); break;
-    case 16: launch_p3<2, 2, 32, 32, 32, 3, BNB, 2>(p, st); break;
-    case 17: launch_p3<2, 2, 32, 32, 32, 2, BNB, 3>(p, st); break;
-    default: launch_p3<2, 2, 64, 32, 64, 2, BNB, 1>(p, st); break;
+    HCB_P3_CFGS(HCB_CASE)
+    default: launch_p3_cfg<BNB, INF>(p, 0, st); break;
   }
 }
+#undef HCB_CASE_TILE
+#undef HCB_CASE_PERSIST
+#undef HCB_CASE_STREAMK
+#undef HCB_CASE_BRES
+#undef HCB_CASE_RETIRED
 
 }  // namespace hcb

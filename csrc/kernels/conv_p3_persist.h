@@ -560,12 +560,12 @@ static bool launch_p3p(const ConvParams& p, hipStream_t st) {
   const bool cbig = (p.C % KW) == 0;
   static bool once = false;
   if (!once) {
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, false, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, false, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, false, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, false, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC>);
     once = true;
   }
   static int cus = 0;
@@ -614,10 +614,10 @@ static bool launch_p3bres(const ConvParams& p, hipStream_t st) {
   const bool cbig = (p.C % KW) == 0;
   static bool once = false;
   if (!once) {
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, 1, false, false, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, 1, false, false, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, 1, false, false, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, 1, false, false, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, 1, false, false, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, 1, false, false, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, 1, false, false, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, 1, false, false, true>);
     once = true;
   }
   static int cus = 0;
@@ -669,10 +669,10 @@ static bool launch_p3sk(const ConvParams& p0, hipStream_t st) {
   const bool cbig = (p.C % KW) == 0;
   static bool once = false;
   if (!once) {
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC, true>);
-    p3_set_lds_once(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC, true>);
+    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, true>);
     once = true;
   }
   static int cus = 0;
@@ -1000,8 +1000,8 @@ static void wlaunch_p3p(const WgradParams& p, int splits, hipStream_t st) {
   const size_t lds = (size_t)2 * NPL * 32 * (BM + BN) * 2;
   static bool once = false;
   if (!once) {
-    p3_set_lds_once(conv_wgrad_p3_persist_kernel<WM, WN, TM, TN, true, OCC>);
-    p3_set_lds_once(conv_wgrad_p3_persist_kernel<WM, WN, TM, TN, false, OCC>);
+    (void)set_lds_max(conv_wgrad_p3_persist_kernel<WM, WN, TM, TN, true, OCC>);
+    (void)set_lds_max(conv_wgrad_p3_persist_kernel<WM, WN, TM, TN, false, OCC>);
     once = true;
   }
   static int cus = 0;

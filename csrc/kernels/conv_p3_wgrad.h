@@ -245,8 +245,8 @@ static void wlaunch_p3(const WgradParams& p, int splits, hipStream_t st) {
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static bool once = false;
   if (!once) {
-    p3_set_lds_once(conv_wgrad_p3_kernel<WM, WN, TM, TN, NST, BK, true, OCC>);
-    p3_set_lds_once(conv_wgrad_p3_kernel<WM, WN, TM, TN, NST, BK, false, OCC>);
+    (void)set_lds_max(conv_wgrad_p3_kernel<WM, WN, TM, TN, NST, BK, true, OCC>);
+    (void)set_lds_max(conv_wgrad_p3_kernel<WM, WN, TM, TN, NST, BK, false, OCC>);
     once = true;
   }
   const dim3 grid(tiles * splits);

@@ -15,7 +15,7 @@
 // are staged through LDS and accumulated with fp32 atomics in 256-byte contiguous rows
 // (the shape the MI355X atomic unit serves at full rate).
 #include "common.h"
-#include "kernels.h"
+#include "igemm_launch.h"
 
 #include <stdlib.h>
 
@@ -805,10 +805,8 @@ static void wlaunch_kq(const WgradParams& p, int splits, hipStream_t st) {
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_kq_kernel<WMt, WNt, KS, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_kq_kernel<WMt, WNt, KS, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)set_lds_max(conv_wgrad_kq_kernel<WMt, WNt, KS, false>);
+    (void)set_lds_max(conv_wgrad_kq_kernel<WMt, WNt, KS, true>);
     once = true;
   }
   const dim3 grid(tiles * splits);
@@ -827,10 +825,8 @@ static void wlaunch_glds(const WgradParams& p, int splits, hipStream_t st) {
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<WM, WN, TM, TN, NST, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<WM, WN, TM, TN, NST, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)set_lds_max(conv_wgrad_glds_kernel<WM, WN, TM, TN, NST, true>);
+    (void)set_lds_max(conv_wgrad_glds_kernel<WM, WN, TM, TN, NST, false>);
     once = true;
   }
   dim3 grid(tiles * splits);
@@ -850,10 +846,8 @@ static void wlaunch(const WgradParams& p, int splits, hipStream_t st) {
   dim3 grid(tiles * splits);
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<WM, WN, TM, TN, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<WM, WN, TM, TN, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)set_lds_max(conv_wgrad_kernel<WM, WN, TM, TN, false>);
+    (void)set_lds_max(conv_wgrad_kernel<WM, WN, TM, TN, true>);
     once = true;
   }
   if (wgrad_one_tap(p, BN))
@@ -862,42 +856,23 @@ static void wlaunch(const WgradParams& p, int splits, hipStream_t st) {
     hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, false>), grid, dim3(256), lds, st, p);
 }
 
-// cfg 0..2: register-staged {128x128, 64x128, 64x64}; 3..9: LDS-DMA ring {128x128 (4 waves of
-// 64x64, NST 4), 128x128 (8 waves of 64x32), 256x128 (8 waves of 64x64), 128x256 (8 waves of
-// 64x64), 64x128 (8 waves of 32x32, NST 4), 64x64 (4 waves, NST 4), 64x128 (4 waves of 64x32,
-// NST 4)}
-// 10-12: intra-workgroup k-split 64x64, 128x64, 64x128; 13-14: register-staged 128x64 / 64x128 with
-// 64x32 / 32x64 wave tiles (twice the MFMAs per loaded row of the 64x64 tile)
-constexpr int N_WGRAD_CFG = 15;
-int wgrad_tile_m(int cfg) {
-  static const int t[N_WGRAD_CFG] = {128, 64, 64, 128, 128, 256, 128, 64, 64, 64, 64, 128, 64, 128, 64};
-  return (cfg >= 0 && cfg < N_WGRAD_CFG) ? t[cfg] : 64;
-}
-int wgrad_tile_n(int cfg) {
-  static const int t[N_WGRAD_CFG] = {128, 128, 64, 128, 128, 128, 256, 128, 64, 128, 64, 64, 128, 64, 128};
-  return (cfg >= 0 && cfg < N_WGRAD_CFG) ? t[cfg] : 64;
-}
-
+// the rows of gemm_cfg.h HCB_WGRAD_CFGS; a cfg outside the table runs cfg 2 (64 x 64). The
+// register-staged loaders keep a thread's 16-byte vector inside one filter tap (every weight pack
+// already requires C % 8 == 0; bindings.cpp checks it)
+#define HCB_CASE_REG(C, WM, WN, TM, TN, NST, KS) \
+  case C: wlaunch<WM, WN, TM, TN>(p, splits, st); break;
+#define HCB_CASE_GLDS(C, WM, WN, TM, TN, NST, KS) \
+  case C: wlaunch_glds<WM, WN, TM, TN, NST>(p, splits, st); break;
+#define HCB_CASE_KQ(C, WM, WN, TM, TN, NST, KS) \
+  case C: wlaunch_kq<WM, WN, KS>(p, splits, st); break;
 void launch_conv_wgrad(const WgradParams& p, int cfg, int splits, hipStream_t st) {
-  // the register-staged loaders keep a thread's 16-byte vector inside one filter tap (every
-  // weight pack already requires C % 8 == 0; bindings.cpp checks it)
   switch (cfg) {
-    case 0: wlaunch<2, 2, 64, 64>(p, splits, st); break;  // 128 x 128
-    case 1: wlaunch<1, 4, 64, 32>(p, splits, st); break;  // 64 x 128
-    case 3: wlaunch_glds<2, 2, 64, 64, 4>(p, splits, st); break;
-    case 4: wlaunch_glds<2, 4, 64, 32, 3>(p, splits, st); break;
-    case 5: wlaunch_glds<4, 2, 64, 64, 3>(p, splits, st); break;
-    case 6: wlaunch_glds<2, 4, 64, 64, 3>(p, splits, st); break;
-    case 7: wlaunch_glds<2, 4, 32, 32, 4>(p, splits, st); break;
-    case 8: wlaunch_glds<2, 2, 32, 32, 4>(p, splits, st); break;
-    case 9: wlaunch_glds<1, 4, 64, 32, 4>(p, splits, st); break;
-    case 10: wlaunch_kq<1, 1, 4>(p, splits, st); break;
-    case 11: wlaunch_kq<2, 1, 2>(p, splits, st); break;
-    case 12: wlaunch_kq<1, 2, 2>(p, splits, st); break;
-    case 13: wlaunch<2, 2, 64, 32>(p, splits, st); break;  // 128 x 64
-    case 14: wlaunch<2, 2, 32, 64>(p, splits, st); break;  // 64 x 128
-    default: wlaunch<2, 2, 32, 32>(p, splits, st); break; // 64 x 64
+    HCB_WGRAD_CFGS(HCB_CASE)
+    default: launch_conv_wgrad(p, 2, splits, st); break;
   }
 }
+#undef HCB_CASE_REG
+#undef HCB_CASE_GLDS
+#undef HCB_CASE_KQ
 
 }  // namespace hcb

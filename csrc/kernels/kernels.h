@@ -8,6 +8,8 @@
 #endif
 #include <stdint.h>
 
+#include "gemm_cfg.h"
+
 namespace hcb {
 
 // Unsigned division by a runtime-invariant divisor: q = (umulhi(n, m) + n) >> s,
@@ -93,17 +95,14 @@ struct ConvParams {
   int64_t y_plane, yres_plane;
 };
 void launch_conv_igemm(const ConvParams& p, int cfg, hipStream_t st);
-// cfg >= CONV_PATCH_CFG0: the 3x3 / stride 1 / pad 1 kernels with the input patch resident in
+// the patch rows of gemm_cfg.h: the 3x3 / stride 1 / pad 1 kernels with the input patch resident in
 // LDS. Returns false (nothing launched) when the problem or the LDS budget does not fit them.
-constexpr int CONV_PATCH_CFG0 = 17;
 bool launch_conv3x3_patch(const ConvParams& p, int cfg, hipStream_t st);
 bool conv3x3_patch_eligible(const ConvParams& p);
 // deterministic reductions (misc.hip): colsum / BN-backward reduce grids limited so that
 // every fp32 accumulator slot receives a single add
 void set_deterministic(bool on);
 bool deterministic();
-int conv_tile_m(int cfg);
-int conv_tile_n(int cfg);
 
 // weight-gradient implicit GEMM: dW[Nout][K] += sum_m dY[m][Nout] * im2col(X)[m][K]
 struct WgradParams {
@@ -121,8 +120,6 @@ struct WgradParams {
   uint32_t dy_plane, x_plane;
 };
 void launch_conv_wgrad(const WgradParams& p, int cfg, int splits, hipStream_t st);
-int wgrad_tile_m(int cfg);
-int wgrad_tile_n(int cfg);
 
 // fp32 convolutions on bf16 hi / mid / lo planes (conv_p3.hip): forward / data-gradient GEMM (x
 // planes, weight packs w / w_lo / w_lo2, fp32 output) and weight gradient (dy and x planes)
@@ -131,12 +128,7 @@ void launch_conv_p3(const ConvParams& p, int cfg, hipStream_t st);
 // (the twin runs; default -- 0.38% slower step with 1, profiles/r6_persistent_bnb.txt), 1 ReLU
 // modes 0 / 2, 2 every mode; initialised from HCB_P3P_BNB
 void set_p3p_bnb(int v);
-int p3_tile_m(int cfg);
-int p3_tile_n(int cfg);
-int p3_slot_k(int cfg);
 void launch_wgrad_p3(const WgradParams& p, int cfg, int splits, hipStream_t st);
-int wgrad_p3_tile_m(int cfg);
-int wgrad_p3_tile_n(int cfg);
 // fp32 [rows][ldx] <-> bf16 planes [3][rows][ldo] (plane stride `plane` elements)
 void launch_split_planes(const float* x, int ldx, int64_t rows, int C, uint16_t* out, int ldo, int64_t plane,
                          hipStream_t st);
