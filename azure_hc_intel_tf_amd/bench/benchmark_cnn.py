@@ -139,7 +139,7 @@ class BenchmarkCNN:
 
     def _build_trainer(self):
         from ..parallel import make_reducer
-        from ..trainer import Trainer
+        from ..trainer import OPT_DEFAULTS, Trainer
 
         p = self.params
         reducer = None
@@ -149,7 +149,13 @@ class BenchmarkCNN:
             reducer = make_reducer(engine, compression=comp)
         self.reducer = reducer
         mom = p.momentum if p.optimizer == "momentum" else 0.0
+        # the hyper-parameters in effect, as the Optimizer: line and the JSON summary show them
+        # (--rmsprop_decay -> decay, --adam_beta1 -> beta1, ...: one flag per Trainer hyper-parameter)
+        self.opt_args = ({"momentum": p.momentum} if p.optimizer == "momentum" else
+                         {k: getattr(p, f"{p.optimizer}_{k}") for k in OPT_DEFAULTS[p.optimizer]})
         self.trainer = Trainer(self.model, self.batch_size, self._lr_fn(), momentum=mom,
+                               optimizer=p.optimizer,
+                               opt_args=self.opt_args if OPT_DEFAULTS[p.optimizer] else None,
                                weight_decay=p.weight_decay, reducer=reducer, world_size=self.size,
                                use_graph=bool(p.use_hip_graph) and self.on_gpu and p.horovod_device != "cpu",
                                forward_only=bool(p.forward_only), label_smoothing=p.label_smoothing,
@@ -182,7 +188,7 @@ class BenchmarkCNN:
         log_fn(f"Data format: {p.data_format} (logical; NHWC kernels)")
         log_fn(f"Precision:   {self.compute_dtype}" + (" (HIP kernels)" if self.model.native else
                                                        " (PyTorch/MIOpen path)" if self.on_gpu else " (CPU)"))
-        log_fn(f"Optimizer:   {p.optimizer}")
+        log_fn(f"Optimizer:   {p.optimizer}" + "".join(f" {k}={v:g}" for k, v in self.opt_args.items()))
         log_fn(f"Variables:   {p.variable_update}")
         log_fn(f"Workers:     {self.size} (one process per {'MI355X' if self.on_gpu else 'CPU worker'})")
         log_fn(f"Params:      {self.model.num_params():,} in {self.model.ps.num_tensors()} tensors")
@@ -216,8 +222,19 @@ class BenchmarkCNN:
         self.loader = loader
         # restore (rank 0) then broadcast_global_variables(0)
         if p.train_dir:
-            step = checkpoint.restore_latest(p.train_dir, self.model.ps) if self.rank == 0 else 0
-            self.step_offset = int(hvd.broadcast_object(step, 0)) if self.size > 1 else step
+            # rank 0 restores; a refusal (the checkpoint of another optimizer family) travels with
+            # the step so that every rank raises it, not rank 0 alone with its peers in a collective
+            step, refused = 0, None
+            if self.rank == 0:
+                try:
+                    step = checkpoint.restore_latest(p.train_dir, self.model.ps)
+                except ValueError as e:
+                    refused = str(e)
+            if self.size > 1:
+                step, refused = hvd.broadcast_object((step, refused), 0)
+            if refused is not None:
+                raise ValueError(refused)
+            self.step_offset = int(step)
             if self.step_offset and self.rank == 0:
                 log_fn(f"Restored checkpoint at step {self.step_offset} from {p.train_dir}")
         self.trainer.steps_done = self.step_offset
@@ -343,6 +360,7 @@ class BenchmarkCNN:
             "gradient_compression": p.gradient_compression, "hip_graph": self.trainer.use_graph,
             "fusion_threshold_bytes": getattr(self.reducer, "bucket_bytes", None),
             "comm": comm,
+            "optimizer": p.optimizer, "optimizer_args": dict(self.opt_args),
         }
         if self.size > 1:
             per_rank = torch.tensor([own_images_per_sec], dtype=torch.float64,

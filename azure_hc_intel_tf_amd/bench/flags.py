@@ -13,6 +13,8 @@ import argparse
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
+from ..optimizers import OPT_DEFAULTS
+
 _TRUE = {"true", "1", "yes", "y", "t", "on"}
 _FALSE = {"false", "0", "no", "n", "f", "off"}
 
@@ -53,7 +55,7 @@ FLAGS: List[Flag] = [
     Flag("kmp_settings", 1, int, "KMP_SETTINGS", noop_on_gpu=True),
     Flag("display_every", 10, int, "log cadence (steps)"),
     Flag("data_format", "NCHW", str, "logical layout (kernels run NHWC internally)", choices=["NCHW", "NHWC"]),
-    Flag("optimizer", "sgd", str, "sgd | momentum", choices=["sgd", "momentum"]),
+    Flag("optimizer", "sgd", str, "sgd | momentum | rmsprop | adam", choices=list(OPT_DEFAULTS)),
     Flag("forward_only", False, parse_bool, "inference-only benchmark (BN from the moving statistics, applied with "
          "the residual add and ReLU in the conv GEMM's epilogue; HCB_FUSE_INFER_BN=0: separate BN passes)"),
     Flag("device", "gpu", str, "gpu (MI355X) or cpu", choices=["gpu", "cpu"]),
@@ -79,6 +81,10 @@ FLAGS: List[Flag] = [
     Flag("fp16_inc_loss_scale_every_n", 1000, int, "double the auto loss scale after N clean steps"),
     Flag("init_learning_rate", None, float, "constant learning rate (overrides the model schedule)"),
     Flag("momentum", 0.9, float, "momentum for --optimizer=momentum"),
+    # --rmsprop_decay / _momentum / _epsilon, --adam_beta1 / _beta2 / _epsilon (TF1 placement of epsilon:
+    # under the square root for rmsprop, added to sqrt(v) for adam)
+    *[Flag(f"{opt}_{k}", v, float, f"{k} for --optimizer={opt}") for opt, args in OPT_DEFAULTS.items()
+      for k, v in args.items()],
     Flag("weight_decay", 0.00004, float, "L2 weight decay (coupled, tf_cnn_benchmarks semantics)"),
     Flag("num_epochs", None, float, "alternative to --num_batches"),
     Flag("train_dir", None, str, "checkpoint directory"),

@@ -15,6 +15,9 @@ momentum buffer and one gradient buffer. This is what makes the hot paths single
 BatchNorm running statistics live in a second flat buffer (``buffers``), and the bf16 GEMM
 operands of every conv (packed [Cout][Kpad] + flipped/transposed [Cin][Kpad_t]) in a bf16
 ``pack`` buffer regenerated from the masters by one multi-tensor kernel per step.
+
+``--optimizer=rmsprop|adam`` add a second flat slot (``slot2``) and, for Adam, the two beta powers
+(``opt_state``), allocated by ``init_optimizer`` only when such an optimizer is selected.
 """
 from __future__ import annotations
 
@@ -86,6 +89,12 @@ class ParamStore:
         self.packs: List[PackRef] = []
         self.gen = torch.Generator().manual_seed(seed)
         self.finalized = False
+        # optimizer state beyond the momentum slot (init_optimizer). optimizer None: no training
+        # run owns this store (inference, tools) -- it has the one momentum slot and nothing else
+        self.optimizer: Optional[str] = None
+        self.slot2 = None      # second flat slot: RMSProp's mean square (starts at ones), Adam's v
+        self.opt_state = None  # Adam: [beta1^t, beta2^t] of the coming step (t from 1), device-advanced
+        self._carried = None   # an unowned store: the rmsprop / adam slots of the checkpoint it loaded
 
     # ------------------------------------------------------------------ registration
     def add(self, name, shape, decay: bool, init, logical_numel: Optional[int] = None) -> ParamRef:
@@ -291,13 +300,58 @@ class ParamStore:
         return len(self.params)
 
     # ------------------------------------------------------------------ state
+    # the optimizers whose slots mean the same thing (a checkpoint moves freely inside a family)
+    OPT_FAMILY = {"sgd": "momentum", "momentum": "momentum", "rmsprop": "rmsprop", "adam": "adam"}
+
+    def init_optimizer(self, kind: str, beta1: float = 0.9, beta2: float = 0.999):
+        """Allocate what ``kind`` needs beyond the momentum slot (Trainer calls this): nothing for
+        sgd / momentum; ``slot2`` for rmsprop (``momentum`` = mom, ``slot2`` = ms) and adam
+        (``momentum`` = m, ``slot2`` = v), plus ``opt_state`` for adam."""
+        if kind not in self.OPT_FAMILY:
+            raise ValueError(f"unknown optimizer {kind!r} (one of {sorted(self.OPT_FAMILY)})")
+        self.optimizer = kind
+        self.slot2 = self.opt_state = self._carried = None
+        if kind == "rmsprop":
+            self.slot2 = torch.ones_like(self.master)
+        elif kind == "adam":
+            self.slot2 = torch.zeros_like(self.master)
+            self.opt_state = torch.tensor([beta1, beta2], dtype=torch.float32, device=self.master.device)
+
     def state_dict(self):
-        return {"master": self.master.detach().cpu(), "momentum": self.momentum.detach().cpu(),
-                "buffers": self.buf.detach().cpu(),
-                "names": [p.name for p in self.params], "offsets": [p.offset for p in self.params]}
+        sd = {"master": self.master.detach().cpu(), "momentum": self.momentum.detach().cpu(),
+              "buffers": self.buf.detach().cpu(),
+              "names": [p.name for p in self.params], "offsets": [p.offset for p in self.params]}
+        if self.slot2 is not None:
+            sd["optimizer"] = self.optimizer
+            sd["slot2"] = self.slot2.detach().cpu()
+            if self.opt_state is not None:
+                sd["opt_state"] = self.opt_state.detach().cpu()
+        elif self.optimizer is None and self._carried:
+            sd.update(self._carried)
+        return sd
 
     def load_state_dict(self, sd):
         assert sd["names"] == [p.name for p in self.params], "checkpoint / model mismatch"
         self.master.copy_(sd["master"].to(self.master.device))
-        self.momentum.copy_(sd["momentum"].to(self.momentum.device))
         self.buf.copy_(sd["buffers"].to(self.buf.device))
+        # (masters and BN buffers are in place: a caller may catch the refusal below and go on
+        # with fresh slots)
+        saved = sd.get("optimizer", "momentum")
+        if self.optimizer is None:
+            # no optimizer owns this store (--forward_only, tools): weights from any checkpoint;
+            # the momentum slot too where the file's slot is one, as before; another family's
+            # slots are carried along untouched, so a checkpoint this store writes loses nothing
+            if self.OPT_FAMILY[saved] == "momentum":
+                self.momentum.copy_(sd["momentum"].to(self.momentum.device))
+                self._carried = None
+            else:
+                self._carried = {k: sd[k] for k in ("optimizer", "momentum", "slot2", "opt_state") if k in sd}
+            return
+        if self.OPT_FAMILY[saved] != self.OPT_FAMILY[self.optimizer]:
+            raise ValueError(f"checkpoint holds the optimizer state of --optimizer={saved}, but this run uses "
+                             f"--optimizer={self.optimizer}: their slots are not interchangeable")
+        self.momentum.copy_(sd["momentum"].to(self.momentum.device))
+        if self.slot2 is not None:
+            self.slot2.copy_(sd["slot2"].to(self.slot2.device))
+        if self.opt_state is not None:
+            self.opt_state.copy_(sd["opt_state"].to(self.opt_state.device))

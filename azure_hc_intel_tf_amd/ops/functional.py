@@ -1403,3 +1403,58 @@ def sgd_momentum(w, mom, g, n_decay, hyper, l2=None, nesterov=False):
         w.sub_(lr * (gg + mu * mom))
     else:
         w.sub_(lr * mom)
+
+
+def _opt_grad_cpu(w, g, n_decay, hyper, l2):
+    """CPU half of the two-slot optimizers: None on a skipped step (found_inf set), else
+    gg = g * grad_scale (+ wd * w over the decayed prefix, the sum rounded once), with sum(w^2) of
+    that prefix added to l2."""
+    if hyper.numel() > 4 and float(hyper[4]) != 0.0:
+        return None
+    gg = g * hyper[3]
+    if n_decay > 0:
+        if l2 is not None:
+            l2 += (w[:n_decay] * w[:n_decay]).sum()
+        # one rounding, as in the kernel: the sum in fp64 (both products are exact there)
+        h = hyper.double()
+        gg[:n_decay] = (g[:n_decay].double() * h[3] + h[2] * w[:n_decay].double()).float()
+    return gg
+
+
+def rmsprop(w, mom, ms, g, n_decay, hyper, ohyper, l2=None):
+    """tf.train.RMSPropOptimizer (not centered) on the flat parameter buffer, one launch:
+    ms = decay*ms + (1-decay)*gg^2; mom = momentum*mom + lr*gg/sqrt(ms+eps); w -= mom, with
+    hyper as in sgd_momentum (hyper[1] unused) and ohyper = [decay, momentum, epsilon] on the
+    device. The CPU branch is the same arithmetic in torch fp32."""
+    if w.is_cuda:
+        _ext.ops().rmsprop(w, mom, ms, g, n_decay, hyper, ohyper, l2)
+        return
+    gg = _opt_grad_cpu(w, g, n_decay, hyper, l2)
+    if gg is None:
+        return
+    decay, mu, eps = ohyper[0], ohyper[1], ohyper[2]
+    ms.mul_(decay).add_((1.0 - decay) * (gg * gg))
+    mom.mul_(mu).add_(hyper[0] * gg / torch.sqrt(ms + eps))
+    w.sub_(mom)
+
+
+def adam(w, m, v, g, n_decay, hyper, ohyper, state, l2=None):
+    """tf.train.AdamOptimizer on the flat parameter buffer: m = b1*m + (1-b1)*gg;
+    v = b2*v + (1-b2)*gg^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps). ohyper = [b1, b2,
+    epsilon]; state = [b1^t, b2^t] of this step on the device (t from 1: it starts as [b1, b2]).
+    Two launches: the update, which only reads state, then the one-thread advance state *= [b1, b2].
+    A skipped step (found_inf) leaves w, both slots and state as they are."""
+    if w.is_cuda:
+        ops = _ext.ops()
+        ops.adam(w, m, v, g, n_decay, hyper, ohyper, state, l2)
+        ops.adam_advance(state, ohyper, hyper)
+        return
+    gg = _opt_grad_cpu(w, g, n_decay, hyper, l2)
+    if gg is None:
+        return
+    b1, b2, eps = ohyper[0], ohyper[1], ohyper[2]
+    lr_t = hyper[0] * torch.sqrt(1.0 - state[1]) / (1.0 - state[0])
+    m.mul_(b1).add_((1.0 - b1) * gg)
+    v.mul_(b2).add_((1.0 - b2) * (gg * gg))
+    w.sub_(lr_t * (m / (torch.sqrt(v) + eps)))
+    state[:2] *= ohyper[:2]

@@ -246,11 +246,15 @@ def broadcast_optimizer_state(optimizer, root_rank: int = 0) -> None:
 
 def broadcast_global_variables(model_or_store, root_rank: int = 0) -> None:
     """hvd.broadcast_global_variables(0) of tf_cnn_benchmarks: every variable of the model
-    (flat fp32 masters, momentum slots and BN moving statistics) from ``root_rank``."""
+    (flat fp32 masters, optimizer slots -- with rmsprop / adam also the second slot and Adam's
+    beta powers -- and BN moving statistics) from ``root_rank``."""
     ps = getattr(model_or_store, "ps", model_or_store)
     broadcast_(ps.master, root_rank)
     broadcast_(ps.momentum, root_rank)
     broadcast_(ps.buf, root_rank)
+    for t in (ps.slot2, ps.opt_state):
+        if t is not None:
+            broadcast_(t, root_rank)
 
 
 class DistributedOptimizer(torch.optim.Optimizer):

@@ -39,6 +39,7 @@ from .nn import layers as L
 from .nn.layers import Logits
 from .ops import functional as Fn
 from .ops import _ext
+from .optimizers import OPT_DEFAULTS
 from .utils.tracing import range_
 
 
@@ -73,7 +74,7 @@ class Trainer:
                  nesterov: bool = False, graph_warmup: int = 2, forward_only: bool = False,
                  loss_scale: Optional[float] = None, dynamic_loss_scale: bool = False,
                  loss_scale_interval: int = 1000, force_overlap: bool = False, comm_check: Optional[bool] = None,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, optimizer: str = "momentum", opt_args: Optional[dict] = None):
         self.model = model
         self.label_smoothing = float(label_smoothing)  # --label_smoothing (the loss kernel's targets)
         self.ps = model.ps
@@ -115,6 +116,31 @@ class Trainer:
         if self.loss_scaling:
             h += [0.0, S, 0.0, float(loss_scale_interval)]
         self.hyper = torch.tensor(h, dtype=torch.float32, device=self.dev)
+        # --optimizer: sgd (momentum 0, the caller's business) and momentum take the one-slot
+        # kernel; rmsprop and adam a second flat slot and their own device hyper-parameters
+        # ohyper = [decay | beta1, momentum | beta2, epsilon, 0] (ParamStore.init_optimizer)
+        if optimizer not in OPT_DEFAULTS:
+            raise ValueError(f"unknown optimizer {optimizer!r} (one of {sorted(OPT_DEFAULTS)})")
+        self.optimizer = optimizer
+        self.opt_args = dict(OPT_DEFAULTS[optimizer])
+        for k, v in (opt_args or {}).items():
+            if k not in self.opt_args:
+                raise ValueError(f"optimizer {optimizer!r} has no hyper-parameter {k!r} "
+                                 f"(it has {sorted(self.opt_args)})")
+            self.opt_args[k] = float(v)
+        self.ohyper = None
+        if not forward_only:
+            a = self.opt_args
+            if optimizer == "rmsprop":
+                self.ps.init_optimizer("rmsprop")
+                self.ohyper = torch.tensor([a["decay"], a["momentum"], a["epsilon"], 0.0], dtype=torch.float32,
+                                           device=self.dev)
+            elif optimizer == "adam":
+                self.ps.init_optimizer("adam", a["beta1"], a["beta2"])
+                self.ohyper = torch.tensor([a["beta1"], a["beta2"], a["epsilon"], 0.0], dtype=torch.float32,
+                                           device=self.dev)
+            else:
+                self.ps.init_optimizer(optimizer)
         self._lr_dev = None  # the learning rate last written to hyper[0]
         self.row_loss = torch.zeros(batch_size, dtype=torch.float32, device=self.dev)
         self.dlogits = torch.zeros((batch_size, ld), dtype=model.act_dtype, device=self.dev)
@@ -197,8 +223,14 @@ class Trainer:
         if self.loss_scaling:
             self.hyper[4:5].zero_()
             Fn.nonfinite(self.ps.grad, self.hyper[4:5])
-        Fn.sgd_momentum(self.ps.master, self.ps.momentum, self.ps.grad, self.ps.n_decay, self.hyper, self.l2,
-                        self.nesterov)
+        ps = self.ps
+        if self.optimizer == "rmsprop":
+            Fn.rmsprop(ps.master, ps.momentum, ps.slot2, ps.grad, ps.n_decay, self.hyper, self.ohyper, self.l2)
+        elif self.optimizer == "adam":
+            Fn.adam(ps.master, ps.momentum, ps.slot2, ps.grad, ps.n_decay, self.hyper, self.ohyper, ps.opt_state,
+                    self.l2)
+        else:
+            Fn.sgd_momentum(ps.master, ps.momentum, ps.grad, ps.n_decay, self.hyper, self.l2, self.nesterov)
         if self.loss_scaling:
             Fn.loss_scale_update(self.hyper, self.world, self.dynamic_ls)
         Fn.loss_total(self.row_loss, self.B, self.l2, 0.5 * self.wd, self.loss)
@@ -463,7 +495,7 @@ class Trainer:
         ps = self.ps
         torch.cuda.synchronize()
         snap = [(t, t.clone()) for t in (ps.master, ps.momentum, ps.buf, ps.persistbuf, self.hyper, self.loss,
-                                          self.row_loss)]
+                                          self.row_loss, ps.slot2, ps.opt_state) if t is not None]
         if self.logits is not None:
             snap.append((self.logits, self.logits.clone()))
         steps = self.steps_done

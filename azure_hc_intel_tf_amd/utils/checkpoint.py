@@ -1,7 +1,8 @@
 """Checkpoint / resume (tf_cnn_benchmarks ``--train_dir`` / ``--save_model_steps`` /
 ``--save_model_secs`` role; SURVEY.md §5 "Checkpoint / resume").
 
-Rank 0 writes ``model.ckpt-<step>.pt`` holding the flat fp32 masters, momentum slots, BN
+Rank 0 writes ``model.ckpt-<step>.pt`` holding the flat fp32 masters, optimizer slots (with
+rmsprop / adam also the second slot, Adam's beta powers and the optimizer's name), BN
 moving statistics and the variable-name table; files contain tensors + plain Python
 containers only and are loaded with ``torch.load(weights_only=True)``. Resume: rank 0
 restores the latest checkpoint, then ``hvd.broadcast_global_variables(0)`` syncs every

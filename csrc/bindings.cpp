@@ -743,6 +743,63 @@ void sgd_momentum(const Tensor& w, const Tensor& mom, const Tensor& g, int64_t n
                            slots, nesterov ? 1 : 0, (int)hyper.numel(), cur_stream());
 }
 
+// the checks the two-slot optimizers share with sgd_momentum; returns the l2 slot count
+int check_opt2(const char* op, const Tensor& w, const Tensor& s1, const Tensor& s2, const Tensor& g,
+               const Tensor& hyper, const Tensor& ohyper, const c10::optional<Tensor>& l2) {
+  check_f32(w, "w");
+  check_f32(s1, "slot");
+  check_f32(s2, "slot2");
+  check_f32(g, "g");
+  check_f32(hyper, "hyper");
+  check_f32(ohyper, "ohyper");
+  TORCH_CHECK(w.is_contiguous() && s1.is_contiguous() && s2.is_contiguous() && g.is_contiguous(), "hcb.", op,
+              ": contiguous");
+  TORCH_CHECK(w.numel() == s1.numel() && w.numel() == s2.numel() && w.numel() == g.numel(), "hcb.", op, ": sizes");
+  check_align16(w.data_ptr(), "w");
+  check_align16(s1.data_ptr(), "slot");
+  check_align16(s2.data_ptr(), "slot2");
+  check_align16(g.data_ptr(), "g");
+  TORCH_CHECK(hyper.numel() >= 4 && hyper.is_contiguous(), "hcb.", op, ": hyper[>=4]");
+  TORCH_CHECK(ohyper.numel() >= 3 && ohyper.is_contiguous(), "hcb.", op, ": ohyper[>=3]");
+  int slots = 0;
+  if (l2.has_value()) {
+    check_f32(*l2, "l2");
+    slots = (int)l2->numel();
+    TORCH_CHECK(l2->is_contiguous() && (slots == 1 || slots >= hcb::sgd_grid(w.numel())), "hcb.", op,
+                ": l2 must hold 1 or >= ", hcb::sgd_grid(w.numel()), " floats");
+  }
+  return slots;
+}
+
+void rmsprop(const Tensor& w, const Tensor& mom, const Tensor& ms, const Tensor& g, int64_t n_decay,
+             const Tensor& hyper, const Tensor& ohyper, const c10::optional<Tensor>& l2) {
+  const int slots = check_opt2("rmsprop", w, mom, ms, g, hyper, ohyper, l2);
+  hcb::launch_rmsprop(w.data_ptr<float>(), mom.data_ptr<float>(), ms.data_ptr<float>(), g.data_ptr<float>(),
+                      w.numel(), n_decay, hyper.data_ptr<float>(), ohyper.data_ptr<float>(),
+                      l2.has_value() ? l2->data_ptr<float>() : nullptr, slots, (int)hyper.numel(), cur_stream());
+}
+
+void adam(const Tensor& w, const Tensor& m, const Tensor& v, const Tensor& g, int64_t n_decay, const Tensor& hyper,
+          const Tensor& ohyper, const Tensor& state, const c10::optional<Tensor>& l2) {
+  const int slots = check_opt2("adam", w, m, v, g, hyper, ohyper, l2);
+  check_f32(state, "state");
+  TORCH_CHECK(state.numel() >= 2 && state.is_contiguous(), "hcb.adam: state[2]");
+  hcb::launch_adam(w.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr<float>(), w.numel(),
+                   n_decay, hyper.data_ptr<float>(), ohyper.data_ptr<float>(), state.data_ptr<float>(),
+                   l2.has_value() ? l2->data_ptr<float>() : nullptr, slots, (int)hyper.numel(), cur_stream());
+}
+
+void adam_advance(const Tensor& state, const Tensor& ohyper, const Tensor& hyper) {
+  check_f32(state, "state");
+  check_f32(ohyper, "ohyper");
+  check_f32(hyper, "hyper");
+  TORCH_CHECK(state.numel() >= 2 && state.is_contiguous(), "hcb.adam_advance: state[2]");
+  TORCH_CHECK(ohyper.numel() >= 3 && ohyper.is_contiguous(), "hcb.adam_advance: ohyper[>=3]");
+  TORCH_CHECK(hyper.numel() >= 4 && hyper.is_contiguous(), "hcb.adam_advance: hyper[>=4]");
+  hcb::launch_adam_advance(state.data_ptr<float>(), ohyper.data_ptr<float>(), hyper.data_ptr<float>(),
+                           (int)hyper.numel(), cur_stream());
+}
+
 void weight_pack(const Tensor& master, const Tensor& pack, const Tensor& table, int64_t max_work, int64_t lo) {
   check_f32(master, "master");
   int64_t pstride = 0;
@@ -1362,6 +1419,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("colsum(Tensor g, int ld, int M, int N, Tensor(a!) out) -> ()");
   m.def("zero_bufs(Tensor(a!)[] ts) -> ()");
   m.def("sgd_momentum(Tensor(a!) w, Tensor(b!) mom, Tensor g, int n_decay, Tensor hyper, Tensor(c!)? l2, bool nesterov) -> ()");
+  m.def("rmsprop(Tensor(a!) w, Tensor(b!) mom, Tensor(c!) ms, Tensor g, int n_decay, Tensor hyper, Tensor ohyper, Tensor(d!)? l2) -> ()");
+  m.def("adam(Tensor(a!) w, Tensor(b!) m, Tensor(c!) v, Tensor g, int n_decay, Tensor hyper, Tensor ohyper, Tensor state, Tensor(d!)? l2) -> ()");
+  m.def("adam_advance(Tensor(a!) state, Tensor ohyper, Tensor hyper) -> ()");
   m.def("weight_pack(Tensor master, Tensor(a!) pack, Tensor table, int max_work, int lo=0) -> ()");
   m.def("cast_f32_bf16(Tensor x, Tensor(a!) y) -> ()");
   m.def("add_bf16(Tensor a, Tensor b, Tensor(a!) y) -> ()");
@@ -1419,6 +1479,9 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("colsum", colsum);
   m.impl("zero_bufs", zero_bufs);
   m.impl("sgd_momentum", sgd_momentum);
+  m.impl("rmsprop", rmsprop);
+  m.impl("adam", adam);
+  m.impl("adam_advance", adam_advance);
   m.impl("weight_pack", weight_pack);
   m.impl("cast_f32_bf16", cast_f32_bf16);
   m.impl("add_bf16", add_bf16);

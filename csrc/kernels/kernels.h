@@ -251,6 +251,15 @@ void launch_colsum2(const void* g, int ld, int M, int N, int is_f32, float* out,
 int sgd_grid(int64_t n);
 void launch_sgd_momentum(float* w, float* mom, const float* g, int64_t n, int64_t n_decay,
                          const float* hyper, float* l2_out, int l2_slots, int nesterov, int hyper_n, hipStream_t st);
+// The two-slot optimizers: same hyper, grid, skip and l2 rules as sgd_momentum (hyper[1] unused).
+// ohyper (device fp32[>=3]): rmsprop [decay, momentum, epsilon], adam [beta1, beta2, epsilon].
+// state (device fp32[2]) = [beta1^t, beta2^t] of the coming step; adam only reads it and
+// adam_advance (one thread, launched after it) multiplies it on unless found_inf is set.
+void launch_rmsprop(float* w, float* mom, float* ms, const float* g, int64_t n, int64_t n_decay, const float* hyper,
+                    const float* ohyper, float* l2_out, int l2_slots, int hyper_n, hipStream_t st);
+void launch_adam(float* w, float* m, float* v, const float* g, int64_t n, int64_t n_decay, const float* hyper,
+                 const float* ohyper, const float* state, float* l2_out, int l2_slots, int hyper_n, hipStream_t st);
+void launch_adam_advance(float* state, const float* ohyper, const float* hyper, int hyper_n, hipStream_t st);
 void launch_nonfinite(const float* g, int64_t n, float* flag, hipStream_t st);
 void launch_loss_total(const float* row_loss, int B, const float* l2, int l2_n, float half_wd, float* loss,
                        hipStream_t st);

@@ -9,6 +9,8 @@
 //     the reported total_loss reduced on the fly) — SURVEY.md §2.6 "ApplyMomentum",
 //     "L2 weight decay"; tf_cnn_benchmarks flags --optimizer=momentum
 //     (/root/reference/benchmark-scripts/run-tf-sing-ucx-openmpi.sh:73).
+//   * rmsprop / adam: tf.train.RMSPropOptimizer / AdamOptimizer (--optimizer=rmsprop|adam) on the
+//     same flat buffers plus a second slot, one launch each; Adam's beta powers are device state.
 //   * weight_pack: one multi-tensor launch producing the bf16 GEMM operands of every
 //     conv from the fp32 masters: [Cout][Kpad] for fwd and the flipped/transposed
 //     [Cin][Kpad_t] for the data gradient.
@@ -226,6 +228,143 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w
     if (l2_slots > 1 && blockIdx.x == 0)
       for (int i = (int)gridDim.x + threadIdx.x; i < l2_slots; i += blockDim.x) l2_out[i] = 0.f;
   }
+}
+
+// ---- the two-slot optimizers (--optimizer=rmsprop|adam): TF1's RMSPropOptimizer (not centered)
+// and AdamOptimizer over the same flat buffers, one launch each. Everything around the
+// per-element rule is sgd_momentum_kernel's: the loss-scaling skip, gg = g * grad_scale (+ wd * w
+// for the decayed prefix), the float4 grid-stride body, the scalar tail and the w^2 partials of
+// the reported loss. `Rule::apply` updates one element in place; IEEE sqrtf and division.
+struct RmspropRule {  // ms = decay*ms + (1-decay)*gg^2; mom = mu*mom + lr*gg/sqrt(ms+eps); w -= mom
+  float lr, decay, omd, mu, eps;
+  __device__ __forceinline__ void apply(float& w, float& mom, float& ms, float gg) const {
+    const float s = decay * ms + omd * (gg * gg);
+    const float m = mu * mom + lr * gg / sqrtf(s + eps);
+    ms = s;
+    mom = m;
+    w -= m;
+  }
+};
+struct AdamRule {  // m = b1*m + (1-b1)*gg; v = b2*v + (1-b2)*gg^2; w -= lr_t * m/(sqrt(v)+eps)
+  float lr_t, b1, omb1, b2, omb2, eps;
+  __device__ __forceinline__ void apply(float& w, float& m, float& v, float gg) const {
+    const float mn = b1 * m + omb1 * gg;
+    const float vn = b2 * v + omb2 * (gg * gg);
+    m = mn;
+    v = vn;
+    w -= lr_t * (mn / (sqrtf(vn) + eps));
+  }
+};
+// the skipped step (hyper[4] set): nothing but the per-block l2 slots is written (zeroed, each
+// slot by one block), exactly as in sgd_momentum_kernel
+__device__ __forceinline__ void opt_skip_l2(float* l2_out, int l2_slots) {
+  if (l2_out != nullptr && l2_slots > 1) {
+    for (int i = threadIdx.x; i < l2_slots; i += blockDim.x)
+      if (i % (int)gridDim.x == (int)blockIdx.x) l2_out[i] = 0.f;
+  }
+}
+// g * grad_scale + wd * w rounded ONCE (both products are exact in fp64): where the two terms
+// cancel, an fp32 sum would carry the products' rounding into every quantity of the step that is
+// proportional to gg (RMSProp's and Adam's updates are; the kernel is memory-bound either way)
+__device__ __forceinline__ float opt2_decayed_grad(float g, float gscale, float wd, float w) {
+  return (float)((double)g * (double)gscale + (double)wd * (double)w);
+}
+template <class Rule>
+__device__ __forceinline__ void opt2_sweep(float* __restrict__ w, float* __restrict__ s1, float* __restrict__ s2,
+                                           const float* __restrict__ g, int64_t n, int64_t n_decay, float wd,
+                                           float gscale, float* l2_out, int l2_slots, const Rule rule) {
+  __shared__ float red[4];
+  float l2 = 0.f;
+  const int64_t n4 = n >> 2;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
+    f32x4 av = reinterpret_cast<f32x4*>(s1)[i];
+    f32x4 bv = reinterpret_cast<f32x4*>(s2)[i];
+    f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      int64_t j = i * 4 + e;
+      float gg = gv[e] * gscale;
+      if (j < n_decay) {
+        gg = opt2_decayed_grad(gv[e], gscale, wd, wv[e]);
+        l2 += wv[e] * wv[e];
+      }
+      float we = wv[e], ae = av[e], be = bv[e];
+      rule.apply(we, ae, be, gg);
+      wv[e] = we;
+      av[e] = ae;
+      bv[e] = be;
+    }
+    reinterpret_cast<f32x4*>(w)[i] = wv;
+    reinterpret_cast<f32x4*>(s1)[i] = av;
+    reinterpret_cast<f32x4*>(s2)[i] = bv;
+  }
+  // scalar tail
+  for (int64_t j = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    float gg = g[j] * gscale;
+    if (j < n_decay) {
+      gg = opt2_decayed_grad(g[j], gscale, wd, w[j]);
+      l2 += w[j] * w[j];
+    }
+    float we = w[j], ae = s1[j], be = s2[j];
+    rule.apply(we, ae, be, gg);
+    w[j] = we;
+    s1[j] = ae;
+    s2[j] = be;
+  }
+  if (l2_out != nullptr) {
+    l2 = wave_sum(l2);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l2;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float t = (red[0] + red[1]) + (red[2] + red[3]);
+      if (l2_slots > 1)
+        l2_out[blockIdx.x] = t;
+      else
+        atomicAdd(l2_out, t);
+    }
+    if (l2_slots > 1 && blockIdx.x == 0)
+      for (int i = (int)gridDim.x + threadIdx.x; i < l2_slots; i += blockDim.x) l2_out[i] = 0.f;
+  }
+}
+// ohyper (device fp32[4]) = [decay, rmsprop_momentum, epsilon, -]
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ w, float* __restrict__ mom,
+                                                      float* __restrict__ ms, const float* __restrict__ g,
+                                                      int64_t n, int64_t n_decay, const float* __restrict__ hyper,
+                                                      const float* __restrict__ ohyper, float* l2_out,
+                                                      int l2_slots, int hyper_n) {
+  if (hyper_n > 4 && hyper[4] != 0.f) {  // wave-uniform: every block exits together
+    opt_skip_l2(l2_out, l2_slots);
+    return;
+  }
+  const float decay = ohyper[0];
+  opt2_sweep(w, mom, ms, g, n, n_decay, hyper[2], hyper[3], l2_out, l2_slots,
+             RmspropRule{hyper[0], decay, 1.f - decay, ohyper[1], ohyper[2]});
+}
+// ohyper = [beta1, beta2, epsilon, -]; state = [beta1^t, beta2^t] of THIS step (t from 1), read
+// only: adam_advance_kernel moves it on after the update, so no block can see a half-advanced t
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ m,
+                                                   float* __restrict__ v, const float* __restrict__ g, int64_t n,
+                                                   int64_t n_decay, const float* __restrict__ hyper,
+                                                   const float* __restrict__ ohyper,
+                                                   const float* __restrict__ state, float* l2_out, int l2_slots,
+                                                   int hyper_n) {
+  if (hyper_n > 4 && hyper[4] != 0.f) {
+    opt_skip_l2(l2_out, l2_slots);
+    return;
+  }
+  const float b1 = ohyper[0], b2 = ohyper[1];
+  const float lr_t = hyper[0] * sqrtf(1.f - state[1]) / (1.f - state[0]);
+  opt2_sweep(w, m, v, g, n, n_decay, hyper[2], hyper[3], l2_out, l2_slots,
+             AdamRule{lr_t, b1, 1.f - b1, b2, 1.f - b2, ohyper[2]});
+}
+// one thread, after adam_kernel: [beta1^t, beta2^t] -> t + 1, unless the step was skipped
+__global__ void adam_advance_kernel(float* state, const float* ohyper, const float* hyper, int hyper_n) {
+  if (hyper_n > 4 && hyper[4] != 0.f) return;
+  state[0] *= ohyper[0];
+  state[1] *= ohyper[1];
 }
 
 __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ x, int64_t n,
@@ -661,6 +800,19 @@ void launch_sgd_momentum(float* w, float* mom, const float* g, int64_t n, int64_
                          const float* hyper, float* l2_out, int l2_slots, int nesterov, int hyper_n, hipStream_t st) {
   hipLaunchKernelGGL(sgd_momentum_kernel, dim3(sgd_grid(n)), dim3(256), 0, st, w, mom, g,
                      n, n_decay, hyper, l2_out, l2_slots, nesterov, hyper_n);
+}
+void launch_rmsprop(float* w, float* mom, float* ms, const float* g, int64_t n, int64_t n_decay, const float* hyper,
+                    const float* ohyper, float* l2_out, int l2_slots, int hyper_n, hipStream_t st) {
+  hipLaunchKernelGGL(rmsprop_kernel, dim3(sgd_grid(n)), dim3(256), 0, st, w, mom, ms, g, n, n_decay, hyper, ohyper,
+                     l2_out, l2_slots, hyper_n);
+}
+void launch_adam(float* w, float* m, float* v, const float* g, int64_t n, int64_t n_decay, const float* hyper,
+                 const float* ohyper, const float* state, float* l2_out, int l2_slots, int hyper_n, hipStream_t st) {
+  hipLaunchKernelGGL(adam_kernel, dim3(sgd_grid(n)), dim3(256), 0, st, w, m, v, g, n, n_decay, hyper, ohyper, state,
+                     l2_out, l2_slots, hyper_n);
+}
+void launch_adam_advance(float* state, const float* ohyper, const float* hyper, int hyper_n, hipStream_t st) {
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, state, ohyper, hyper, hyper_n);
 }
 void launch_l2norm_sq(const float* x, int64_t n, float* out, hipStream_t st) {
   hipLaunchKernelGGL(l2norm_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, out);

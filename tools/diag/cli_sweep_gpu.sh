@@ -75,6 +75,8 @@ run r50_trace $R50 --trace_file=$OUT/trace.json
 run r50_accuracy_smoothing $R50 --print_training_accuracy=True --label_smoothing=0.1
 run r50_eager $R50 --use_hip_graph=False
 run r50_sgd_nhwc $R50 --optimizer=sgd --data_format=NHWC
+run r50_rmsprop $R50 --optimizer=rmsprop --rmsprop_epsilon=1.0
+run r50_adam_fp16 $R50 --optimizer=adam --use_fp16=True
 run r50_comm_check $R50 --comm_check=True --variable_update=horovod
 run r50_compress_fp16 $R50 --gradient_compression=fp16 --variable_update=horovod
 run r50_comm_torch $R50 --comm_engine=torch --variable_update=horovod
