@@ -127,7 +127,80 @@ class Layer:
         pass
 
 
-class ConvBN(Layer):
+class _BatchNorm(Layer):
+    """The BatchNorm half of ConvBN (and StemS2D) and of BNReLU: its parameters and buffers, and the
+    one place where their bundle is spelled out for the ``Fn.bn_*`` calls. The layer provides
+    ``relu``, ``eps``, ``decay`` and ``out_shape``."""
+
+    _acc = None  # (fwd acc, bwd acc, replicas) of the current step
+
+    def _init_bn(self, ps: ParamStore, name: str, C: int, scale: bool = True):
+        if scale:
+            self.gamma = ps.add(f"{name}/batchnorm/gamma", (C,), False, ParamStore.const(1.0))
+        else:  # tf batch_norm(scale=False): gamma fixed at 1, not a variable
+            self.gamma = _FixedParam(ps.add_buffer(f"{name}/batchnorm/gamma_fixed", (C,), 1.0),
+                                     ps.add_buffer(f"{name}/batchnorm/gamma_grad_sink", (C,), 0.0))
+        self.beta = ps.add(f"{name}/batchnorm/beta", (C,), False, ParamStore.const(0.0))
+        self.rmean = ps.add_buffer(f"{name}/batchnorm/moving_mean", (C,), 0.0)
+        self.rvar = ps.add_buffer(f"{name}/batchnorm/moving_variance", (C,), 1.0)
+        # GPU: statistic accumulators (R replicas of [2][C]) and saved batch moments
+        self.acc_f = ps.add_stat(f"{name}/bn_acc_fwd", (STAT_R, 2, C))
+        self.acc_b = ps.add_stat(f"{name}/bn_acc_bwd", (STAT_R, 2, C))
+        self.sv_mean = ps.add_stat(f"{name}/bn_mean", (C,))
+        self.sv_invstd = ps.add_stat(f"{name}/bn_invstd", (C,))
+        # statistics shift K: the previous step's batch mean (written by the BN backward); the
+        # producer accumulates (v - K) so the single-pass variance does not cancel (|mean| >> std)
+        self.shift = ps.add_persist(f"{name}/bn_shift", (C,)) if BN_SHIFT else None
+
+    def _stat_bufs(self, N: int, dev):
+        """(forward acc, backward acc, replicas) of this step's BN statistics: the persistent
+        STAT_R-replica buffers, or in deterministic mode fresh ones with a replica per 64 rows
+        (each fp32 slot then receives a single add)."""
+        if not Fn.deterministic():
+            self._acc = (self.acc_f.data, self.acc_b.data, STAT_R)
+        else:
+            P, Q, C = self.out_shape
+            R = Fn.det_replicas(N * P * Q)
+            self._acc = (torch.zeros((R, 2, C), dtype=torch.float32, device=dev),
+                         torch.zeros((R, 2, C), dtype=torch.float32, device=dev), R)
+        return self._acc
+
+    def _shift(self):
+        return self.shift.data if self.shift is not None else None
+
+    def _bn_params(self):
+        return self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data
+
+    def _bn_inference(self, z, y, residual=None):
+        return Fn.bn_inference(z, *self._bn_params(), self.eps, y, self.relu, residual=residual)
+
+    def _bn_forward_acc(self, z, y, residual=None, res_bn=None):
+        """Finalize-free GPU BN of z from this step's forward accumulator (``_stat_bufs``)."""
+        acc_f, _, R = self._acc
+        return Fn.bn_forward_acc(z, *self._bn_params(), self.decay, self.eps, y, self.relu, acc_f, R,
+                                 self.sv_mean.data, self.sv_invstd.data, residual=residual, shift=self._shift(),
+                                 res_bn=res_bn)
+
+    def _bn_backward_acc(self, dy, y, z, saved, relu_mode, dz, gres=None, **kw):
+        """GPU BN backward through this step's backward accumulator; leaves the next step's shift."""
+        _, acc_b, R = self._acc
+        return Fn.bn_backward_acc(dy, y, z, saved, self.gamma.data, self.beta.data, relu_mode, self.gamma.grad,
+                                  self.beta.grad, dz, acc_b, R, gres, shift_out=self._shift(), **kw)
+
+    def _bn_forward_ref(self, z, y, residual=None):
+        return Fn.bn_forward(z, *self._bn_params(), self.decay, self.eps, y, self.relu, residual=residual)
+
+    def _bn_backward_ref(self, dy, y, z, saved, relu_mode, dz, gres=None):
+        return Fn.bn_backward(dy, y, z, saved, self.gamma.data, self.beta.data, relu_mode, self.gamma.grad,
+                              self.beta.grad, dz, gres)
+
+    def res_bn_args(self):
+        """The residual-BN operands of a deferred BN (bn_forward_acc res_bn)."""
+        return (self._acc[0], self.gamma.data, self.beta.data, self.sv_mean.data, self.sv_invstd.data,
+                self.rmean.data, self.rvar.data, self._shift())
+
+
+class ConvBN(_BatchNorm):
     """conv(k x k, stride, padding) -> BatchNorm(train) -> [residual add] -> [ReLU]."""
 
     _pool_fused = None  # the Pool whose forward ran fused into this layer's BN (forward_maxpool)
@@ -157,46 +230,17 @@ class ConvBN(Layer):
         self.w = ps.add(f"{name}/conv2d/kernel", (cout, kh, kw, cin), True, winit, logical_numel=cout * kh * kw * lc)
         self.pack = ps.add_pack(self.w, cout, kh, kw, cin, self.spec.Kpad, self.spec.Kpad_t, want_tr=need_dx)
         if bn:
-            if scale:
-                self.gamma = ps.add(f"{name}/batchnorm/gamma", (cout,), False, ParamStore.const(1.0))
-            else:  # tf batch_norm(scale=False): gamma fixed at 1, not a variable
-                self.gamma = _FixedParam(ps.add_buffer(f"{name}/batchnorm/gamma_fixed", (cout,), 1.0),
-                                         ps.add_buffer(f"{name}/batchnorm/gamma_grad_sink", (cout,), 0.0))
-            self.beta = ps.add(f"{name}/batchnorm/beta", (cout,), False, ParamStore.const(0.0))
-            self.rmean = ps.add_buffer(f"{name}/batchnorm/moving_mean", (cout,), 0.0)
-            self.rvar = ps.add_buffer(f"{name}/batchnorm/moving_variance", (cout,), 1.0)
-            # GPU: statistic accumulators (R replicas of [2][C]) and saved batch moments
-            self.acc_f = ps.add_stat(f"{name}/bn_acc_fwd", (STAT_R, 2, cout))
-            self.acc_b = ps.add_stat(f"{name}/bn_acc_bwd", (STAT_R, 2, cout))
-            self.sv_mean = ps.add_stat(f"{name}/bn_mean", (cout,))
-            self.sv_invstd = ps.add_stat(f"{name}/bn_invstd", (cout,))
-            # statistics shift K: the previous step's batch mean (written by the BN backward); the
-            # epilogue accumulates (v - K) so the single-pass variance does not cancel (|mean| >> std)
-            self.shift = ps.add_persist(f"{name}/bn_shift", (cout,)) if BN_SHIFT else None
+            self._init_bn(ps, name, cout, scale)
         else:
             # ResNet-v2's un-normalised convs (shortcut, conv3) have no bias in tf_cnn_benchmarks
             self.bias = ps.add(f"{name}/conv2d/bias", (cout,), True, ParamStore.const(0.0)) if bias else None
         self._saved = None
-        self._acc = None  # (fwd acc, bwd acc, replicas) of the current step
         self._pre_reduced = False
         self.training = True  # False: inference BN from the moving statistics (forward-only)
 
     def flops(self, batch: int) -> int:
         P, Q, C = self.out_shape
         return 2 * batch * P * Q * C * self.spec.kh * self.spec.kw * self.spec.cin
-
-    def _stat_bufs(self, N: int, dev):
-        """(forward acc, backward acc, replicas) of this step's BN statistics: the persistent
-        STAT_R-replica buffers, or in deterministic mode fresh ones with a replica per 64 rows
-        (each fp32 slot then receives a single add)."""
-        if not Fn.deterministic():
-            self._acc = (self.acc_f.data, self.acc_b.data, STAT_R)
-        else:
-            P, Q, C = self.out_shape
-            R = Fn.det_replicas(N * P * Q)
-            self._acc = (torch.zeros((R, 2, C), dtype=torch.float32, device=dev),
-                         torch.zeros((R, 2, C), dtype=torch.float32, device=dev), R)
-        return self._acc
 
     def params(self):
         """Trainable ParamRefs of this layer (gradient slots in the flat buffer)."""
@@ -219,12 +263,6 @@ class ConvBN(Layer):
         self._saved = (x, z, None, Fn.BNSaved(self.sv_mean.data, self.sv_invstd.data), False)
         return z
 
-    def res_bn_args(self):
-        """The residual-BN operands of a deferred BN (bn_forward_acc res_bn)."""
-        acc_f, _, _ = self._acc
-        return (acc_f, self.gamma.data, self.beta.data, self.sv_mean.data, self.sv_invstd.data, self.rmean.data,
-                self.rvar.data, self._shift())
-
     def forward(self, x, out=None, residual=None, residual_bn=None):
         """``residual_bn``: the ConvBN (run with forward_deferred) whose raw output ``residual``
         is BN-normalised inside this layer's BN pass before the add."""
@@ -234,8 +272,7 @@ class ConvBN(Layer):
         if self.bn and not self.training and FUSE_INFER_BN:
             y = out if out is not None else empty_op((N, P, Q, C), dev)
             Fn.conv_bn_inference(x, self.spec, self.pack.pack if Fn.native(x) else None, self.w.data,
-                                 self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
-                                 self.relu, residual=residual)
+                                 *self._bn_params(), self.eps, y, self.relu, residual=residual)
             self._saved = None
             return y
         if self.bn and not self.training:
@@ -244,29 +281,22 @@ class ConvBN(Layer):
             if Fn.planes_mode() and Fn.native(x) and not Fn.is_planes(x):  # fp32 path: the GEMM operand as planes
                 x = Fn.to_planes(x)
             Fn.conv_forward(x, self.spec, self.pack.pack if Fn.native(x) else None, self.w.data, z)
-            Fn.bn_inference(z, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
-                            self.relu, residual=residual)
             self._saved = None
-            return y
+            return self._bn_inference(z, y, residual)
         if self.bn:
             z = empty_act((N, P, Q, C), dev)
             if Fn.native(x):
                 y = out if out is not None else empty_op((N, P, Q, C), dev)
                 # conv epilogue accumulates the batch statistics; the apply kernel finalizes them
                 x = self._conv_fwd_stats(x, z)
-                acc_f, _, R = self._acc
                 if residual_bn is not None:
-                    assert residual_bn._acc[2] == R, "residual BN accumulators must match the replica count"
-                saved = Fn.bn_forward_acc(z, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data,
-                                          self.decay, self.eps, y, self.relu, acc_f, R,
-                                          self.sv_mean.data, self.sv_invstd.data, residual=residual,
-                                          shift=self._shift(),
-                                          res_bn=residual_bn.res_bn_args() if residual_bn is not None else None)
+                    assert residual_bn._acc[2] == self._acc[2], "residual BN accumulators must match the replica count"
+                saved = self._bn_forward_acc(z, y, residual,
+                                             residual_bn.res_bn_args() if residual_bn is not None else None)
             else:
                 y = out if out is not None else empty_act((N, P, Q, C), dev)
                 Fn.conv_forward(x, self.spec, None, self.w.data, z)
-                saved = Fn.bn_forward(z, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data,
-                                      self.decay, self.eps, y, self.relu, residual=residual)
+                saved = self._bn_forward_ref(z, y, residual)
             self._saved = (x, z, y, saved, residual is not None)
             return y
         assert residual is None or not self.relu, "conv without BN: residual add only without ReLU"
@@ -295,9 +325,8 @@ class ConvBN(Layer):
         y = (empty_op if out_planes else empty_act)((N,) + tuple(pool.out_shape), x.device)
         amax = torch.empty((N,) + tuple(pool.out_shape), dtype=torch.uint8, device=x.device)
         acc_f, _, R = self._acc
-        saved = Fn.bn_relu_maxpool_acc(z, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.decay,
-                                       self.eps, acc_f, R, self.sv_mean.data, self.sv_invstd.data, y,
-                                       amax, *pool.k, *pool.s, pool.pads, shift=self._shift())
+        saved = Fn.bn_relu_maxpool_acc(z, *self._bn_params(), self.decay, self.eps, acc_f, R, self.sv_mean.data,
+                                       self.sv_invstd.data, y, amax, *pool.k, *pool.s, pool.pads, shift=self._shift())
         self._saved = (x, z, None, saved, False)
         pool._saved = (z, y, amax)  # the argmax backward reads only shapes from x / y
         self._pool_fused = pool
@@ -316,10 +345,7 @@ class ConvBN(Layer):
         P, Q, _ = pool.out_shape
         pt, _, pl, _ = pool.pads
         dz = empty_op((N, H, W, C), dyp.device)
-        _, acc_b, R = self._acc
-        Fn.bn_backward_acc(dyp, None, z, saved, self.gamma.data, self.beta.data, 2, self.gamma.grad, self.beta.grad,
-                           dz, acc_b, R, None, shift_out=self._shift(),
-                           pool=(amax, [H, W, P, Q, pool.k[0], pool.s[0], pt, pl]))
+        self._bn_backward_acc(dyp, None, z, saved, 2, dz, pool=(amax, [H, W, P, Q, pool.k[0], pool.s[0], pt, pl]))
         run_wgrad(self, dz, x)
         self._saved = None
         self._pool_fused = None
@@ -334,9 +360,6 @@ class ConvBN(Layer):
         Fn.conv_forward(x, self.spec, self.pack.pack, self.w.data, z, stats=acc_f, stats_R=R,
                         stats_shift=self._shift())
         return x
-
-    def _shift(self):
-        return self.shift.data if self.shift is not None else None
 
     def _wgrad(self, dz, x):
         Fn.conv_wgrad(dz, x, self.spec, self.w.grad.view(dz.shape[-1], -1) if Fn.native(dz) else self.w.grad)
@@ -368,12 +391,9 @@ class ConvBN(Layer):
             self._pre_reduced = False
             dz = empty_op((N, P, Q, C), dev) if Fn.native(dy) else empty_act((N, P, Q, C), dev)
             if Fn.native(dy):
-                _, acc_b, R = self._acc
-                Fn.bn_backward_acc(dy, None, z, saved, self.gamma.data, self.beta.data, 0, self.gamma.grad,
-                                   self.beta.grad, dz, acc_b, R, None, pre_reduced=True, shift_out=self._shift())
+                self._bn_backward_acc(dy, None, z, saved, 0, dz, pre_reduced=True)
             else:
-                Fn.bn_backward(dy, y, z, saved, self.gamma.data, self.beta.data, 0, self.gamma.grad,
-                               self.beta.grad, dz, None)
+                self._bn_backward_ref(dy, y, z, saved, 0, dz)
             if want_gres:
                 gres = dy
         elif self.bn:
@@ -382,12 +402,9 @@ class ConvBN(Layer):
                 gres = empty_act((N, P, Q, C), dev)
             relu_mode = (1 if had_res else 2) if self.relu else 0
             if Fn.native(dy):
-                _, acc_b, R = self._acc
-                Fn.bn_backward_acc(dy, y, z, saved, self.gamma.data, self.beta.data, relu_mode, self.gamma.grad,
-                                   self.beta.grad, dz, acc_b, R, gres, shift_out=self._shift())
+                self._bn_backward_acc(dy, y, z, saved, relu_mode, dz, gres)
             else:
-                Fn.bn_backward(dy, y, z, saved, self.gamma.data, self.beta.data, relu_mode, self.gamma.grad,
-                               self.beta.grad, dz, gres)
+                self._bn_backward_ref(dy, y, z, saved, relu_mode, dz, gres)
         else:
             if self.relu:
                 if Fn.native(dy) and not (dy.is_contiguous() and y.is_contiguous()):
@@ -552,8 +569,7 @@ class StemS2D(ConvBN):
         if not self.training and FUSE_INFER_BN:
             y = out if out is not None else empty_op((N, P, Q, C), x.device)
             Fn.conv_bn_inference(self.fold_input(x), self.fold_spec, self._folded_weight(x.device), self.w.data,
-                                 self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
-                                 self.relu, residual=residual)
+                                 *self._bn_params(), self.eps, y, self.relu, residual=residual)
             self._saved = None
             return y
         z = empty_act((N, P, Q, C), x.device)
@@ -561,16 +577,10 @@ class StemS2D(ConvBN):
         if not self.training:
             xf = self.fold_input(x)
             Fn.conv_forward(xf, self.fold_spec, self._folded_weight(x.device), self.w.data, z)
-            Fn.bn_inference(z, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
-                            self.relu, residual=residual)
             self._saved = None
-            return y
+            return self._bn_inference(z, y, residual)
         xf = self._conv_fwd_stats(x, z)
-        acc_f, _, R = self._acc
-        saved = Fn.bn_forward_acc(z, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.decay,
-                                  self.eps, y, self.relu, acc_f, R, self.sv_mean.data,
-                                  self.sv_invstd.data, residual=residual, shift=self._shift())
-        self._saved = (xf, z, y, saved, residual is not None)
+        self._saved = (xf, z, y, self._bn_forward_acc(z, y, residual), residual is not None)
         return y
 
     def tune_view(self):
@@ -632,7 +642,7 @@ class Pool(Layer):
         self._saved = None
 
 
-class BNReLU(Layer):
+class BNReLU(_BatchNorm):
     """Standalone training-mode BatchNorm (+ ReLU) on an activation: the pre-activation of
     ResNet v2 blocks (tf_cnn_benchmarks ``bottleneck_block_v2``: preact = relu(batch_norm(x)))
     and its final BN. There is no producing GEMM epilogue to fuse the statistics into: on the GPU
@@ -650,44 +660,26 @@ class BNReLU(Layer):
         self.relu = relu
         self.eps = eps
         self.decay = decay
-        self.gamma = ps.add(f"{name}/batchnorm/gamma", (C,), False, ParamStore.const(1.0))
-        self.beta = ps.add(f"{name}/batchnorm/beta", (C,), False, ParamStore.const(0.0))
-        self.rmean = ps.add_buffer(f"{name}/batchnorm/moving_mean", (C,), 0.0)
-        self.rvar = ps.add_buffer(f"{name}/batchnorm/moving_variance", (C,), 1.0)
-        self.acc_f = ps.add_stat(f"{name}/bn_acc_fwd", (STAT_R, 2, C))
-        self.acc_b = ps.add_stat(f"{name}/bn_acc_bwd", (STAT_R, 2, C))
-        self.sv_mean = ps.add_stat(f"{name}/bn_mean", (C,))
-        self.sv_invstd = ps.add_stat(f"{name}/bn_invstd", (C,))
-        self.shift = ps.add_persist(f"{name}/bn_shift", (C,)) if BN_SHIFT else None
+        self._init_bn(ps, name, C)
         self._saved = None
-        self._acc = None
         self.training = True
 
     def params(self):
         return [self.beta, self.gamma]
 
-    _stat_bufs = ConvBN._stat_bufs
-    _shift = ConvBN._shift
-
     def forward(self, x):
         if Fn.is_planes(x):  # (the fp32 path's pooled stem output when not produced in fp32)
             x = Fn.from_planes(x)
         if not self.training:
-            y = empty_act(tuple(x.shape), x.device)
-            return Fn.bn_inference(x, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.eps, y,
-                                   self.relu)
+            return self._bn_inference(x, empty_act(tuple(x.shape), x.device))
         if Fn.native(x):
-            N, H, W, C = x.shape
-            acc_f, _, R = self._stat_bufs(N, x.device)
+            acc_f, _, R = self._stat_bufs(x.shape[0], x.device)
             Fn.bn_stats_acc(x, acc_f, R, self._shift())
             y = empty_op(tuple(x.shape), x.device)
-            saved = Fn.bn_forward_acc(x, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.decay,
-                                      self.eps, y, self.relu, acc_f, R, self.sv_mean.data, self.sv_invstd.data,
-                                      shift=self._shift())
+            saved = self._bn_forward_acc(x, y)
         else:
             y = empty_act(tuple(x.shape), x.device)
-            saved = Fn.bn_forward(x, self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data, self.decay,
-                                  self.eps, y, self.relu)
+            saved = self._bn_forward_ref(x, y)
         self._saved = (x, y, saved)
         return y
 
@@ -697,13 +689,9 @@ class BNReLU(Layer):
         dx = empty_act(tuple(x.shape), dy.device)
         dy = dy if dy.is_contiguous() else dy.contiguous()
         if Fn.native(dy):
-            _, acc_b, R = self._acc
-            Fn.bn_backward_acc(dy, None, x, saved, self.gamma.data, self.beta.data, 2 if self.relu else 0,
-                               self.gamma.grad, self.beta.grad, dx, acc_b, R, None, shift_out=self._shift(),
-                               add=add)
+            self._bn_backward_acc(dy, None, x, saved, 2 if self.relu else 0, dx, add=add)
         else:
-            Fn.bn_backward(dy, y, x, saved, self.gamma.data, self.beta.data, 1 if self.relu else 0, self.gamma.grad,
-                           self.beta.grad, dx)
+            self._bn_backward_ref(dy, y, x, saved, 1 if self.relu else 0, dx)
             if add is not None:
                 dx.add_(add)
         self._saved = None

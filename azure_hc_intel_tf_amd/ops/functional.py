@@ -1008,24 +1008,13 @@ def bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu: bool
     return out
 
 
-def bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, out, relu: bool,
-               residual=None, stats=None, stats_T: int = 0):
-    """Training BN: batch stats (from a fused conv slab when given), running-stat update,
-    out = act(gamma*xhat + beta [+ residual])."""
+def bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, out, relu: bool, residual=None):
+    """Training BN, the PyTorch reference path (CPU, and the GPU's reference-precision dtypes): batch
+    stats, running-stat update, out = act(gamma*xhat + beta [+ residual]). A native tensor takes
+    bn_stats_acc (or the producing conv's epilogue) + bn_forward_acc."""
+    assert not native(z), "native BN forward: bn_stats_acc + bn_forward_acc"
     N, H, W, C = z.shape
     M = N * H * W
-    if native(z):
-        hcb = _ext.ops()
-        if stats is None:
-            stats_T = hcb.bn_partials(M, C)
-            stats = torch.empty(stats_T * 2 * C, dtype=torch.float32, device=z.device)
-            hcb.bn_stats(z, M, C, ld(z), stats)
-        mean = torch.empty(C, dtype=torch.float32, device=z.device)
-        invstd = torch.empty_like(mean)
-        hcb.bn_finalize(stats, stats_T, C, float(M), eps, momentum, mean, invstd, running_mean, running_var)
-        hcb.bn_apply(z, ld(z), out, ld(out), residual, ld(residual) if residual is not None else 0, M, C,
-                     mean, invstd, gamma, beta, 1 if relu else 0)
-        return BNSaved(mean, invstd)
     zf = z.reshape(M, C) if z.is_contiguous() else z.contiguous().reshape(M, C)
     if zf.dtype == torch.float16:  # fused batch norm keeps its statistics in fp32 (TF semantics)
         zf = zf.float()
@@ -1128,20 +1117,11 @@ def bn_backward_acc(dy, y, z, saved: BNSaved, gamma, beta, relu_mode: int, dgamm
 def bn_backward(dy, y, z, saved: BNSaved, gamma, beta, relu_mode: int, dgamma, dbeta, dz, gres=None):
     """BN(+ReLU) backward. relu_mode: 0 none, 1 mask from stored output y (residual blocks),
     2 mask recomputed from z. Writes dgamma/dbeta (fp32, overwrite), dz, and optionally the
-    masked upstream gradient gres (the residual branch's gradient)."""
+    masked upstream gradient gres (the residual branch's gradient). The PyTorch reference path, as
+    bn_forward is; a native tensor takes bn_backward_acc."""
+    assert not native(z), "native BN backward: bn_backward_acc"
     N, H, W, C = z.shape
     M = N * H * W
-    if native(z):
-        hcb = _ext.ops()
-        T = hcb.bn_partials(M, C)
-        slab = torch.empty(T * 2 * C, dtype=torch.float32, device=z.device)
-        hcb.bn_bwd_reduce(dy, ld(dy), y if relu_mode == 1 else None, ld(y) if relu_mode == 1 else 0, z, ld(z),
-                          M, C, saved.mean, saved.invstd, gamma, beta, relu_mode, slab, gres,
-                          ld(gres) if gres is not None else 0)
-        hcb.bn_bwd_finalize(slab, T, C, dgamma, dbeta)
-        hcb.bn_bwd_apply(dy, ld(dy), y if relu_mode == 1 else None, ld(y) if relu_mode == 1 else 0, z, ld(z),
-                         dz, ld(dz), M, C, saved.mean, saved.invstd, gamma, beta, dgamma, dbeta, relu_mode)
-        return dz
     if z.dtype == torch.float16:  # backward reductions in fp32 as well
         z, dy = z.float(), dy.float()
         y = y.float() if y is not None else None

@@ -399,41 +399,6 @@ void conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArra
   hcb::launch_conv_wgrad(p, (int)cfg, eff_splits, cur_stream());
 }
 
-void bn_stats(const Tensor& x, int64_t M, int64_t C, int64_t ldx, const Tensor& slab) {
-  check_act(x, "x");
-  check_f32(slab, "slab");
-  TORCH_CHECK(C % 8 == 0 && C <= 2048 && ldx % 8 == 0, "hcb.bn_stats: C % 8 == 0, C <= 2048");
-  check_range(x, ((M - 1) * ldx + C) * 2, "x");
-  int T = hcb::bn_num_partials((int)M, (int)C);
-  TORCH_CHECK(slab.numel() >= (int64_t)T * 2 * C, "hcb.bn_stats: slab too small");
-  hcb::launch_bn_stats(x.data_ptr(), (int)M, (int)C, (int)ldx, slab.data_ptr<float>(), T, cur_stream());
-}
-
-int64_t bn_partials(int64_t M, int64_t C) { return hcb::bn_num_partials((int)M, (int)C); }
-
-void bn_finalize(const Tensor& slab, int64_t T, int64_t C, double count, double eps, double momentum,
-                 const Tensor& mean, const Tensor& invstd, const c10::optional<Tensor>& rm,
-                 const c10::optional<Tensor>& rv) {
-  check_f32(slab, "slab");
-  check_f32(mean, "mean");
-  check_f32(invstd, "invstd");
-  TORCH_CHECK(slab.numel() >= T * 2 * C && mean.numel() >= C && invstd.numel() >= C, "hcb.bn_finalize: sizes");
-  float* rmp = nullptr;
-  float* rvp = nullptr;
-  if (rm.has_value() && rv.has_value()) {
-    check_f32(*rm, "running_mean");
-    check_f32(*rv, "running_var");
-    rmp = rm->data_ptr<float>();
-    rvp = rv->data_ptr<float>();
-  }
-  TORCH_CHECK(C <= 64 * 64, "hcb.bn_finalize: C too large");
-  Tensor part = at::empty({(int64_t)hcb::bn_finalize_splits((int)T) * 2 * C},
-                          at::TensorOptions().dtype(at::kDouble).device(slab.device()));
-  hcb::launch_bn_finalize_split(slab.data_ptr<float>(), (int)T, (int)C, part.data_ptr<double>(), 1, count,
-                                (float)eps, (float)momentum, mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                                rmp, rvp, nullptr, nullptr, cur_stream());
-}
-
 void bn_apply(const Tensor& x, int64_t ldx, const Tensor& y, int64_t ldy, const c10::optional<Tensor>& res,
               int64_t ldr, int64_t M, int64_t C, const Tensor& mean, const Tensor& invstd,
               const Tensor& gamma, const Tensor& beta, int64_t relu) {
@@ -452,70 +417,6 @@ void bn_apply(const Tensor& x, int64_t ldx, const Tensor& y, int64_t ldy, const 
   hcb::launch_bn_apply(x.data_ptr(), (int)ldx, y.data_ptr(), (int)ldy, rp, (int)ldr, (int)M, (int)C,
                        mean.data_ptr<float>(), invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                        beta.data_ptr<float>(), (int)relu, cur_stream());
-}
-
-void bn_bwd_reduce(const Tensor& dy, int64_t lddy, const c10::optional<Tensor>& y, int64_t ldyv,
-                   const Tensor& x, int64_t ldx, int64_t M, int64_t C, const Tensor& mean,
-                   const Tensor& invstd, const Tensor& gamma, const Tensor& beta, int64_t relu,
-                   const Tensor& slab, const c10::optional<Tensor>& gout, int64_t ldg) {
-  check_act(dy, "dy");
-  check_act(x, "x");
-  check_f32(slab, "slab");
-  TORCH_CHECK(C % 8 == 0 && C <= 2048, "hcb.bn_bwd_reduce: C");
-  check_range(dy, ((M - 1) * lddy + C) * 2, "dy");
-  check_range(x, ((M - 1) * ldx + C) * 2, "x");
-  const void* yp = nullptr;
-  if (relu == 1) {
-    TORCH_CHECK(y.has_value(), "hcb.bn_bwd_reduce: relu=1 needs y");
-    check_range(*y, ((M - 1) * ldyv + C) * 2, "y");
-    yp = y->data_ptr();
-  }
-  void* gp = nullptr;
-  if (gout.has_value()) {
-    check_act(*gout, "gout");
-    check_range(*gout, ((M - 1) * ldg + C) * 2, "gout");
-    gp = gout->data_ptr();
-  }
-  int T = hcb::bn_num_partials((int)M, (int)C);
-  TORCH_CHECK(slab.numel() >= (int64_t)T * 2 * C, "hcb.bn_bwd_reduce: slab too small");
-  hcb::launch_bn_bwd_reduce2(dy.data_ptr(), (int)lddy, yp, (int)ldyv, x.data_ptr(), (int)ldx, (int)M,
-                             (int)C, mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                             gamma.data_ptr<float>(), beta.data_ptr<float>(), (int)relu,
-                             slab.data_ptr<float>(), T, gp, (int)ldg, cur_stream());
-}
-
-void bn_bwd_finalize(const Tensor& slab, int64_t T, int64_t C, const Tensor& dgamma, const Tensor& dbeta) {
-  check_f32(slab, "slab");
-  check_f32(dgamma, "dgamma");
-  check_f32(dbeta, "dbeta");
-  TORCH_CHECK(C <= 64 * 64 && slab.numel() >= T * 2 * C, "hcb.bn_bwd_finalize: sizes");
-  Tensor part = at::empty({(int64_t)hcb::bn_finalize_splits((int)T) * 2 * C},
-                          at::TensorOptions().dtype(at::kDouble).device(slab.device()));
-  hcb::launch_bn_finalize_split(slab.data_ptr<float>(), (int)T, (int)C, part.data_ptr<double>(), 0, 0.0, 0.f,
-                                0.f, nullptr, nullptr, nullptr, nullptr, dgamma.data_ptr<float>(),
-                                dbeta.data_ptr<float>(), cur_stream());
-}
-
-void bn_bwd_apply(const Tensor& dy, int64_t lddy, const c10::optional<Tensor>& y, int64_t ldyv,
-                  const Tensor& x, int64_t ldx, const Tensor& dx, int64_t lddx, int64_t M, int64_t C,
-                  const Tensor& mean, const Tensor& invstd, const Tensor& gamma, const Tensor& beta,
-                  const Tensor& dgamma, const Tensor& dbeta, int64_t relu) {
-  check_act(dy, "dy");
-  check_act(x, "x");
-  check_act(dx, "dx");
-  check_range(dy, ((M - 1) * lddy + C) * 2, "dy");
-  check_range(x, ((M - 1) * ldx + C) * 2, "x");
-  check_range(dx, ((M - 1) * lddx + C) * 2, "dx");
-  const void* yp = nullptr;
-  if (relu == 1) {
-    TORCH_CHECK(y.has_value(), "hcb.bn_bwd_apply: relu=1 needs y");
-    check_range(*y, ((M - 1) * ldyv + C) * 2, "y");
-    yp = y->data_ptr();
-  }
-  hcb::launch_bn_bwd_apply2(dy.data_ptr(), (int)lddy, yp, (int)ldyv, x.data_ptr(), (int)ldx,
-                            dx.data_ptr(), (int)lddx, (int)M, (int)C, mean.data_ptr<float>(),
-                            invstd.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                            dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), (int)relu, cur_stream());
 }
 
 // geom = [N,H,W,C,P,Q,ldy,kh,kw,sh,sw,ph,pw]; z contiguous [N,H,W,C]
@@ -1400,13 +1301,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
   m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);
   m.def("conv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int[] geom, int cfg, int splits) -> ()");
-  m.def("bn_stats(Tensor x, int M, int C, int ldx, Tensor(a!) slab) -> ()");
-  m.def("bn_partials(int M, int C) -> int", bn_partials);
-  m.def("bn_finalize(Tensor slab, int T, int C, float count, float eps, float momentum, Tensor(a!) mean, Tensor(b!) invstd, Tensor(c!)? running_mean, Tensor(d!)? running_var) -> ()");
   m.def("bn_apply(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu) -> ()");
-  m.def("bn_bwd_reduce(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu, Tensor(a!) slab, Tensor(b!)? gout, int ldg) -> ()");
-  m.def("bn_bwd_finalize(Tensor slab, int T, int C, Tensor(a!) dgamma, Tensor(b!) dbeta) -> ()");
-  m.def("bn_bwd_apply(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, Tensor(a!) dx, int lddx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor dgamma, Tensor dbeta, int relu) -> ()");
   m.def("pool_fwd(Tensor x, Tensor(a!) y, Tensor(b!)? idx, int[] geom) -> ()");
   m.def("pool_bwd(Tensor dy, Tensor x, Tensor y, Tensor? idx, Tensor(a!) dx, int[] geom, bool accumulate) -> ()");
   m.def("pool_fwd_p3(Tensor x, Tensor(a!) y, Tensor(b!)? idx, int[] geom) -> ()");
@@ -1464,12 +1359,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("loss_scale_update", loss_scale_update);
   m.impl("set_splitk_workspace", set_splitk_workspace);
   m.impl("conv_wgrad", conv_wgrad);
-  m.impl("bn_stats", bn_stats);
-  m.impl("bn_finalize", bn_finalize);
   m.impl("bn_apply", bn_apply);
-  m.impl("bn_bwd_reduce", bn_bwd_reduce);
-  m.impl("bn_bwd_finalize", bn_bwd_finalize);
-  m.impl("bn_bwd_apply", bn_bwd_apply);
   m.impl("pool_fwd", pool_fwd);
   m.impl("pool_bwd", pool_bwd);
   m.impl("pool_fwd_p3", pool_fwd_p3);

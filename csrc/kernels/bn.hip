@@ -1,16 +1,28 @@
-// Training-mode batch normalisation for NHWC bf16 activations on gfx950
-// (the MKL-DNN FusedBatchNorm fwd/bwd role; tf_cnn_benchmarks ResNet
-// config decay=0.9, eps=1e-5, scale=True).
+// Training-mode batch normalisation for NHWC activations on gfx950 (the MKL-DNN FusedBatchNorm
+// fwd/bwd role; tf_cnn_benchmarks ResNet config decay=0.9, eps=1e-5, scale=True).
+// T = the build's 16-bit type (bf16 / fp16) or fp32, whose GEMM operands are bf16 hi / mid / lo planes.
 //
-// Layout: x is [M = N*H*W][C] with C contiguous. Every thread owns one 16-byte vector of
-// 8 channels, keeps that channel vector's scale/shift (or partial sums) in registers and
-// walks rows, so every global access is a 16-byte coalesced load/store and the per
-// channel parameters are read once per thread (guide: always vectorize bf16).
+// Layout: x is [M = N*H*W][C] with C contiguous. Every thread owns one vector of 8 channels, keeps
+// that channel vector's scale/shift (or partial sums) in registers and walks rows, so every global
+// access is a 16-byte (16-bit data) or 32-byte coalesced load/store and the per-channel parameters
+// are read once per thread (guide: always vectorize bf16).
 //
-// Statistics are reduced in two levels: per-block partial sums in an fp32 slab
-// [T][2][C] (the conv epilogue writes the same slab format, so stats can be fused into
-// the producing GEMM), then a finalize kernel that sums the slab in fp64 — no float
-// atomics, bitwise reproducible.
+// Statistics live in R replicas of an fp32 [2][C] accumulator, zeroed once per step by one memset:
+// sum(v - K) and sum((v - K)^2) for the forward (K = the layer's shift, its previous batch mean),
+// sum(g) and sum(g * xhat) for the backward. Producers add their block / tile partials with fp32
+// atomics into replica (block or tile index) % R, which spreads the contention:
+//   * forward: the conv GEMM epilogue of the layer's own conv, or bn_stats_acc_kernel for a BN whose
+//     input is not a GEMM output (ResNet v2's pre-activation and final BN);
+//   * backward: bn_bwd_reduce_acc_kernel, or the data-gradient GEMM epilogue that produced dy.
+// Consumers finalize in-kernel: every block of bn_apply_acc_kernel, bn_relu_maxpool_acc_kernel and
+// bn_bwd_apply_acc_kernel sums the replicas of its own channel group and derives mean / invstd (or
+// dgamma / dbeta) itself, and block 0 publishes them with the running statistics and the next
+// step's shift -- there is no finalize launch. Deterministic mode caps the producer grids at R row
+// blocks, so every replica slot receives a single add.
+//
+// bn_apply_kernel is the one kernel outside that scheme: the plain affine apply from a given mean
+// and invstd, which inference runs from the moving statistics on 16-bit data (an unfused conv + BN
+// layer, and the standalone BN of ResNet v2, in forward-only mode).
 #include <cstdlib>
 
 #include "common.h"
@@ -28,7 +40,7 @@ __device__ __forceinline__ uint32_t rsrc_bytes(int M, int ld, int esz = 2) {
   return b > 0x7fffffffu ? 0x7fffffffu : (uint32_t)b;
 }
 
-// thread -> (channel vector, row lane) mapping shared by all kernels below
+// thread -> (channel vector, row lane) mapping of bn_apply_kernel (a block spans all C channels)
 struct RowMap {
   int cv, r0, rstep, active;
 };
@@ -41,114 +53,6 @@ __device__ __forceinline__ RowMap rowmap(int C) {
   m.rstep = rows;
   m.active = m.r0 < rows;
   return m;
-}
-
-// reduce per-thread partial (s1, s2) over threads sharing a channel vector, write slab row
-__device__ __forceinline__ void slab_write(float* lds, const float* s1, const float* s2, int C,
-                                           const RowMap& rm, float* slab_row) {
-  int CV = C >> 3;
-  int rows = 256 / CV;
-  // lds: [rows][C] for s1 then s2
-  if (rm.active) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      lds[rm.r0 * C + rm.cv * 8 + e] = s1[e];
-      lds[rows * C + rm.r0 * C + rm.cv * 8 + e] = s2[e];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    float a = 0.f, b = 0.f;
-    for (int r = 0; r < rows; ++r) {
-      a += lds[r * C + c];
-      b += lds[rows * C + r * C + c];
-    }
-    slab_row[c] = a;
-    slab_row[C + c] = b;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restrict__ x, int M, int C,
-                                                       int ldx, float* slab) {
-  extern __shared__ __attribute__((aligned(16))) float lds_f[];
-  RowMap rm = rowmap(C);
-  float s1[8] = {0}, s2[8] = {0};
-  if (rm.active) {
-    for (int m = blockIdx.x * rm.rstep + rm.r0; m < M; m += gridDim.x * rm.rstep) {
-      u32x4 v = *reinterpret_cast<const u32x4*>(x + (size_t)m * ldx + rm.cv * 8);
-      float f[8];
-      unpack8(v, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        s1[e] += f[e];
-        s2[e] += f[e] * f[e];
-      }
-    }
-  }
-  slab_write(lds_f, s1, s2, C, rm, slab + (size_t)blockIdx.x * 2 * C);
-}
-
-// Parallel slab reduction: a block owns 64 channels (one per lane, so every load is a
-// 256-byte coalesced row segment); its 8 waves stride over the T partial rows with 4
-// independent loads in flight each, accumulate in fp64, then combine through LDS.
-constexpr int FIN_WAVES = 8;
-__device__ __forceinline__ void slab_reduce64(const float* slab, int T, int C, double* a_out,
-                                              double* b_out, double* lds) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  double a = 0.0, b = 0.0;
-  if (c < C) {
-    int t = wid;
-    for (; t + 3 * FIN_WAVES < T; t += 4 * FIN_WAVES) {
-      float x0 = slab[(size_t)t * 2 * C + c], y0 = slab[(size_t)t * 2 * C + C + c];
-      float x1 = slab[(size_t)(t + FIN_WAVES) * 2 * C + c], y1 = slab[(size_t)(t + FIN_WAVES) * 2 * C + C + c];
-      float x2 = slab[(size_t)(t + 2 * FIN_WAVES) * 2 * C + c],
-            y2 = slab[(size_t)(t + 2 * FIN_WAVES) * 2 * C + C + c];
-      float x3 = slab[(size_t)(t + 3 * FIN_WAVES) * 2 * C + c],
-            y3 = slab[(size_t)(t + 3 * FIN_WAVES) * 2 * C + C + c];
-      a += ((double)x0 + (double)x1) + ((double)x2 + (double)x3);
-      b += ((double)y0 + (double)y1) + ((double)y2 + (double)y3);
-    }
-    for (; t < T; t += FIN_WAVES) {
-      a += (double)slab[(size_t)t * 2 * C + c];
-      b += (double)slab[(size_t)t * 2 * C + C + c];
-    }
-  }
-  lds[wid * 64 + lane] = a;
-  lds[FIN_WAVES * 64 + wid * 64 + lane] = b;
-  __syncthreads();
-  if (wid == 0) {
-    a = 0.0;
-    b = 0.0;
-#pragma unroll
-    for (int w = 0; w < FIN_WAVES; ++w) {
-      a += lds[w * 64 + lane];
-      b += lds[FIN_WAVES * 64 + w * 64 + lane];
-    }
-  }
-  *a_out = a;
-  *b_out = b;
-}
-
-__global__ __launch_bounds__(512) void bn_finalize_kernel(const float* slab, int T, int C, double count,
-                                                          float eps, float momentum, float* mean,
-                                                          float* invstd, float* run_mean,
-                                                          float* run_var) {
-  __shared__ double lds[2 * FIN_WAVES * 64];
-  double a, b;
-  slab_reduce64(slab, T, C, &a, &b, lds);
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  if ((threadIdx.x >> 6) != 0 || c >= C) return;
-  double mu = a / count;
-  double var = b / count - mu * mu;
-  if (var < 0.0) var = 0.0;
-  mean[c] = (float)mu;
-  invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (run_mean != nullptr) {
-    double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    run_mean[c] = (float)(momentum * run_mean[c] + (1.0 - momentum) * mu);
-    run_var[c] = (float)(momentum * run_var[c] + (1.0 - momentum) * unbiased);
-  }
 }
 
 __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restrict__ x, int ldx,
@@ -202,43 +106,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
   }
 }
 
-// relu: 0 = none, 1 = mask from stored output y (y > 0), 2 = mask recomputed from x
-// (gamma*xhat + beta > 0; valid when the block had no residual add)
-struct BwdSrc {
-  __amdgpu_buffer_rsrc_t dyr, xr, yr;
-  int lddy, ldx, ldyv, cv;
-  __device__ __forceinline__ void load(int m, int M, int relu, u32x4& d, u32x4& x, u32x4& y) const {
-    const bool ok = m < M;
-    d = buf_load16(dyr, ok ? (uint32_t)((size_t)m * lddy + cv * 8) * 2u : HCB_OOB);
-    x = buf_load16(xr, ok ? (uint32_t)((size_t)m * ldx + cv * 8) * 2u : HCB_OOB);
-    if (relu == 1) y = buf_load16(yr, ok ? (uint32_t)((size_t)m * ldyv + cv * 8) * 2u : HCB_OOB);
-  }
-};
-__device__ __forceinline__ void bwd_math(const u32x4& dv, const u32x4& xvv, const u32x4& yvv, int relu,
-                                         const float* mu, const float* is, const float* sc, const float* sh,
-                                         float* g, float* xh) {
-  float d[8], xv[8];
-  unpack8(dv, d);
-  unpack8(xvv, xv);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) xh[e] = (xv[e] - mu[e]) * is[e];
-  if (relu == 1) {
-    float yv[8];
-    unpack8(yvv, yv);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = yv[e] > 0.f ? d[e] : 0.f;
-  } else if (relu == 2) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (xv[e] * sc[e] + sh[e]) > 0.f ? d[e] : 0.f;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = d[e];
-  }
-}
-
-// element-type generic forms (T = the build's 16-bit type or fp32) used by the finalize-free kernels
-// TY: element type of the ReLU-mask source y -- T, or (fp32 path) uint16_t: the bf16 hi plane of the
-// plane-stored activation (hi > 0 exactly when y > 0 for every normal y)
 // BN backward fed straight from a max-pool's gradient (the ResNet stem: BN -> ReLU -> 3x3/2 max
 // pool): dy of pixel (n, h, w) is gathered from the pooled gradient dyp of the <= 2x2 windows that
 // contain it and whose argmax (amax, window-local index per channel) is this pixel -- the
@@ -276,6 +143,11 @@ __device__ __forceinline__ void pool_gather(const PoolSrc& ps, int m, int M, int
   d.set_f(g);
 }
 
+// The backward kernels' operands, by element type: T = the build's 16-bit type or fp32; TY = element
+// type of the ReLU-mask source y -- T, or (fp32 path) uint16_t: the bf16 hi plane of the plane-stored
+// activation (hi > 0 exactly when y > 0 for every normal y).
+// relu: 0 = none, 1 = mask from stored output y (y > 0), 2 = mask recomputed from x
+// (gamma*xhat + beta > 0; valid when the block had no residual add)
 template <typename T, typename TY = T, bool POOL = false>
 struct BwdSrcT {
   __amdgpu_buffer_rsrc_t dyr, xr, yr;
@@ -315,224 +187,12 @@ __device__ __forceinline__ void bwd_math_t(const Act8<T>& dv, const Act8<T>& xvv
   }
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
-    const uint16_t* __restrict__ dy, int lddy, const uint16_t* __restrict__ y, int ldyv,
-    const uint16_t* __restrict__ x, int ldx, int M, int C, const float* mean, const float* invstd,
-    const float* gamma, const float* beta, int relu, float* slab, uint16_t* gout, int ldg) {
-  extern __shared__ __attribute__((aligned(16))) float lds_f[];
-  RowMap rm = rowmap(C);
-  float s1[8] = {0}, s2[8] = {0};
-  if (rm.active) {
-    float mu[8], is[8], sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int c = rm.cv * 8 + e;
-      mu[e] = mean[c];
-      is[e] = invstd[c];
-      sc[e] = gamma != nullptr ? gamma[c] * is[e] : 0.f;
-      sh[e] = beta != nullptr ? beta[c] - mu[e] * sc[e] : 0.f;
-    }
-    BwdSrc src{make_rsrc(dy, rsrc_bytes(M, lddy)), make_rsrc(x, rsrc_bytes(M, ldx)),
-               make_rsrc(y != nullptr ? y : x, rsrc_bytes(M, y != nullptr ? ldyv : ldx)), lddy, ldx, ldyv, rm.cv};
-    const int stride = gridDim.x * rm.rstep;
-    for (int m0 = blockIdx.x * rm.rstep + rm.r0; m0 < M; m0 += BN_U * stride) {
-      u32x4 dv[BN_U], xv[BN_U], yv[BN_U];
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) src.load(m0 + u * stride, M, relu, dv[u], xv[u], yv[u]);
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        const int m = m0 + u * stride;
-        float g[8], xh[8];
-        bwd_math(dv[u], xv[u], yv[u], relu, mu, is, sc, sh, g, xh);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {  // rows beyond M load zeros: g = 0 contributes nothing
-          s1[e] += g[e];
-          s2[e] += g[e] * xh[e];
-        }
-        if (gout != nullptr && m < M) *reinterpret_cast<u32x4*>(gout + (size_t)m * ldg + rm.cv * 8) = pack8(g);
-      }
-    }
-  }
-  slab_write(lds_f, s1, s2, C, rm, slab + (size_t)blockIdx.x * 2 * C);
-}
-
-__global__ __launch_bounds__(512) void bn_bwd_finalize_kernel(const float* slab, int T, int C,
-                                                              float* dgamma, float* dbeta) {
-  __shared__ double lds[2 * FIN_WAVES * 64];
-  double a, b;
-  slab_reduce64(slab, T, C, &a, &b, lds);
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  if ((threadIdx.x >> 6) != 0 || c >= C) return;
-  dbeta[c] = (float)a;
-  dgamma[c] = (float)b;
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
-    const uint16_t* __restrict__ dy, int lddy, const uint16_t* __restrict__ y, int ldyv,
-    const uint16_t* __restrict__ x, int ldx, uint16_t* __restrict__ dx, int lddx, int M, int C,
-    const float* mean, const float* invstd, const float* gamma, const float* beta,
-    const float* dgamma, const float* dbeta, int relu) {
-  RowMap rm = rowmap(C);
-  if (!rm.active) return;
-  float mu[8], is[8], sc[8], sh[8], k1[8], k2[8];
-  const float invM = 1.f / (float)M;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    int c = rm.cv * 8 + e;
-    mu[e] = mean[c];
-    is[e] = invstd[c];
-    sc[e] = gamma[c] * is[e];
-    sh[e] = beta[c] - mu[e] * sc[e];
-    k1[e] = dbeta[c] * invM;
-    k2[e] = dgamma[c] * invM;
-  }
-  BwdSrc src{make_rsrc(dy, rsrc_bytes(M, lddy)), make_rsrc(x, rsrc_bytes(M, ldx)),
-             make_rsrc(y != nullptr ? y : x, rsrc_bytes(M, y != nullptr ? ldyv : ldx)), lddy, ldx, ldyv, rm.cv};
-  const int stride = gridDim.x * rm.rstep;
-  for (int m0 = blockIdx.x * rm.rstep + rm.r0; m0 < M; m0 += BN_U * stride) {
-    u32x4 dv[BN_U], xv[BN_U], yv[BN_U];
-#pragma unroll
-    for (int u = 0; u < BN_U; ++u) src.load(m0 + u * stride, M, relu, dv[u], xv[u], yv[u]);
-#pragma unroll
-    for (int u = 0; u < BN_U; ++u) {
-      const int m = m0 + u * stride;
-      float g[8], xh[8], o[8];
-      bwd_math(dv[u], xv[u], yv[u], relu, mu, is, sc, sh, g, xh);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = sc[e] * (g[e] - k1[e] - xh[e] * k2[e]);
-      if (m < M) *reinterpret_cast<u32x4*>(dx + (size_t)m * lddx + rm.cv * 8) = pack8(o);
-    }
-  }
-}
-
 static int bn_grid(int M, int C) {
   int rows = 256 / (C / 8);
   int need = (M + rows - 1) / rows;
   // ~4 blocks per CU over 256 CUs; each block loops over its rows
   int g = need < 1024 ? need : 1024;
   return g < 1 ? 1 : g;
-}
-
-int bn_num_partials(int M, int C) { return bn_grid(M, C); }
-
-// ---------------------------------------------------------------------------------------
-// One-launch two-level finalize. Grid (C/64 channel groups) x (S row splits): each block
-// reduces T/S slab rows for 64 channels (fp64) into part[S][2][C]; the LAST block of a
-// channel group (agent-scope release -> ticket atomic -> acquire, the placement-independent
-// hand-off of the CDNA guide, Guideline 16) sums the S partials and writes the outputs, then
-// re-arms its counter. Counters start zeroed at module load and are left zeroed by every
-// launch, so graph replays need no memset.
-__device__ unsigned g_fin_counters[64];
-
-template <bool FWD>
-__global__ __launch_bounds__(512) void bn_finalize_split_kernel(
-    const float* __restrict__ slab, int T, int C, int rows_per, double* part, double count, float eps,
-    float momentum, float* mean, float* invstd, float* run_mean, float* run_var, float* dgamma,
-    float* dbeta) {
-  __shared__ double lds[2 * FIN_WAVES * 64];
-  __shared__ int last;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  const int S = gridDim.y;
-  const int t0 = blockIdx.y * rows_per;
-  const int t1 = min(T, t0 + rows_per);
-  double a = 0.0, b = 0.0;
-  if (c < C) {
-    for (int t = t0 + wid; t < t1; t += FIN_WAVES) {
-      a += (double)slab[(size_t)t * 2 * C + c];
-      b += (double)slab[(size_t)t * 2 * C + C + c];
-    }
-  }
-  lds[wid * 64 + lane] = a;
-  lds[FIN_WAVES * 64 + wid * 64 + lane] = b;
-  __syncthreads();
-  if (wid == 0 && c < C) {
-    a = 0.0;
-    b = 0.0;
-#pragma unroll
-    for (int w = 0; w < FIN_WAVES; ++w) {
-      a += lds[w * 64 + lane];
-      b += lds[FIN_WAVES * 64 + w * 64 + lane];
-    }
-    part[(size_t)blockIdx.y * 2 * C + c] = a;
-    part[(size_t)blockIdx.y * 2 * C + C + c] = b;
-  }
-  // publish: every storing wave drains, barrier, one release + ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned tk = __hip_atomic_fetch_add(&g_fin_counters[blockIdx.x], 1u, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
-    last = (tk == (unsigned)(S - 1));
-  }
-  __syncthreads();
-  if (!last) return;
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-  if (wid != 0) return;
-  if (c < C) {
-    a = 0.0;
-    b = 0.0;
-    for (int s = 0; s < S; ++s) {
-      a += part[(size_t)s * 2 * C + c];
-      b += part[(size_t)s * 2 * C + C + c];
-    }
-    if constexpr (FWD) {
-      double mu = a / count;
-      double var = b / count - mu * mu;
-      if (var < 0.0) var = 0.0;
-      mean[c] = (float)mu;
-      invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-      if (run_mean != nullptr) {
-        double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        run_mean[c] = (float)(momentum * run_mean[c] + (1.0 - momentum) * mu);
-        run_var[c] = (float)(momentum * run_var[c] + (1.0 - momentum) * unbiased);
-      }
-    } else {
-      dbeta[c] = (float)a;
-      dgamma[c] = (float)b;
-    }
-  }
-  if (lane == 0) __hip_atomic_store(&g_fin_counters[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-int bn_finalize_splits(int T) {
-  int s = (T + 63) / 64;
-  return s < 1 ? 1 : (s > 32 ? 32 : s);
-}
-
-void launch_bn_finalize_split(const float* slab, int T, int C, double* part, int fwd, double count, float eps,
-                              float momentum, float* mean, float* invstd, float* run_mean, float* run_var,
-                              float* dgamma, float* dbeta, hipStream_t st) {
-  int S = bn_finalize_splits(T);
-  int rows_per = (T + S - 1) / S;
-  S = (T + rows_per - 1) / rows_per;
-  dim3 grid((C + 63) / 64, S);
-  if (fwd)
-    hipLaunchKernelGGL(bn_finalize_split_kernel<true>, grid, dim3(64 * FIN_WAVES), 0, st, slab, T, C, rows_per,
-                       part, count, eps, momentum, mean, invstd, run_mean, run_var, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL(bn_finalize_split_kernel<false>, grid, dim3(64 * FIN_WAVES), 0, st, slab, T, C, rows_per,
-                       part, 0.0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, dgamma, dbeta);
-}
-
-void launch_bn_stats(const void* x, int M, int C, int ldx, float* slab, int T, hipStream_t st) {
-  int rows = 256 / (C / 8);
-  size_t lds = (size_t)2 * rows * C * 4;
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(T), dim3(256), lds, st, (const uint16_t*)x, M, C, ldx,
-                     slab);
-}
-
-void launch_bn_finalize(const float* slab, int T, int C, double count, float eps, float momentum,
-                        float* mean, float* invstd, float* run_mean, float* run_var,
-                        hipStream_t st) {
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, st, slab, T, C,
-                     count, eps, momentum, mean, invstd, run_mean, run_var);
 }
 
 void launch_bn_apply(const void* x, int ldx, void* y, int ldy, const void* res, int ldr, int M,
@@ -543,47 +203,11 @@ void launch_bn_apply(const void* x, int ldx, void* y, int ldy, const void* res, 
                      beta, relu);
 }
 
-void launch_bn_bwd_reduce2(const void* dy, int lddy, const void* y, int ldyv, const void* x,
-                           int ldx, int M, int C, const float* mean, const float* invstd,
-                           const float* gamma, const float* beta, int relu, float* slab, int T,
-                           void* gout, int ldg, hipStream_t st) {
-  int rows = 256 / (C / 8);
-  size_t lds = (size_t)2 * rows * C * 4;
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(T), dim3(256), lds, st, (const uint16_t*)dy, lddy,
-                     (const uint16_t*)y, ldyv, (const uint16_t*)x, ldx, M, C, mean, invstd, gamma,
-                     beta, relu, slab, (uint16_t*)gout, ldg);
-}
-
-void launch_bn_bwd_finalize(const float* slab, int T, int C, float* dgamma, float* dbeta,
-                            hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, st, slab, T, C,
-                     dgamma, dbeta);
-}
-
-void launch_bn_bwd_apply2(const void* dy, int lddy, const void* y, int ldyv, const void* x, int ldx,
-                          void* dx, int lddx, int M, int C, const float* mean, const float* invstd,
-                          const float* gamma, const float* beta, const float* dgamma,
-                          const float* dbeta, int relu, hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_grid(M, C)), dim3(256), 0, st,
-                     (const uint16_t*)dy, lddy, (const uint16_t*)y, ldyv, (const uint16_t*)x, ldx,
-                     (uint16_t*)dx, lddx, M, C, mean, invstd, gamma, beta, dgamma, dbeta, relu);
-}
-
-}  // namespace hcb
-
-
 // =======================================================================================
-// Finalize-free BN: statistics are accumulated with fp32 atomics into R replicas of a
-// [2][C] accumulator (producer tile t adds into replica t % R, spreading the contention);
-// the consumer kernel reduces the replicas itself and derives mean/invstd (or dgamma/dbeta),
-// which removes the separate finalize launch per BN layer (two per layer per step).
-// Accumulators are zeroed once per step by one memset.
-//
-// Blocks tile (row split) x (channel group of CB = 8*CVB channels): a block reduces only
+// The replica-accumulator kernels. Blocks tile (row split) x (channel group of CB = 8*CVB channels): a block reduces only
 // its group's R*2*CB replica floats (4 KiB for CB = 64) instead of all C channels, and a
 // row segment of a group is CB*2 = 128 contiguous bytes, so loads stay line-sized.
 // =======================================================================================
-namespace hcb {
 
 // channel vectors (of 8) per group: 8 when possible, else the whole (small) C, else the
 // largest divisor <= 32

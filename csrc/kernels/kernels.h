@@ -138,36 +138,10 @@ void launch_merge_planes(const uint16_t* in, int ldi, int64_t plane, int64_t row
 void launch_gap_fwd_p3(const uint16_t* x, int64_t xps, uint16_t* y, int64_t yps, int N, int HW, int C, hipStream_t st);
 
 // ---------------------------------------------------------------- batch norm
-// stats slab [T][2][C] -> mean, invstd (fp32) and running stats update
-void launch_bn_finalize(const float* slab, int T, int C, double count, float eps, float momentum,
-                        float* mean, float* invstd, float* run_mean, float* run_var,
-                        hipStream_t st);
-// stats directly from an activation tensor [M][C] (when not fused into the producer)
-void launch_bn_stats(const void* x, int M, int C, int ldx, float* slab, int T, hipStream_t st);
-// y = act(gamma*(x-mean)*invstd + beta [+ res])
+// y = act(gamma*(x-mean)*invstd + beta [+ res]) from a given mean / invstd, 16-bit data (inference)
 void launch_bn_apply(const void* x, int ldx, void* y, int ldy, const void* res, int ldr, int M,
                      int C, const float* mean, const float* invstd, const float* gamma,
                      const float* beta, int relu, hipStream_t st);
-int bn_num_partials(int M, int C);
-// one-launch finalize (split rows + last-block combine); part: fp64 scratch [32][2][C]
-int bn_finalize_splits(int T);
-void launch_bn_finalize_split(const float* slab, int T, int C, double* part, int fwd, double count, float eps,
-                              float momentum, float* mean, float* invstd, float* run_mean, float* run_var,
-                              float* dgamma, float* dbeta, hipStream_t st);
-// backward reduce: g = dy*mask (relu: 0 none, 1 mask y>0, 2 mask recomputed from x);
-// per-block partial sums of g and g*xhat -> slab; optionally writes g to gout
-void launch_bn_bwd_reduce2(const void* dy, int lddy, const void* y, int ldyv, const void* x,
-                           int ldx, int M, int C, const float* mean, const float* invstd,
-                           const float* gamma, const float* beta, int relu, float* slab, int T,
-                           void* gout, int ldg, hipStream_t st);
-// dgamma/dbeta from slab
-void launch_bn_bwd_finalize(const float* slab, int T, int C, float* dgamma, float* dbeta,
-                            hipStream_t st);
-// dx = gamma*invstd*(g - dbeta/M - xhat*dgamma/M)
-void launch_bn_bwd_apply2(const void* dy, int lddy, const void* y, int ldyv, const void* x,
-                          int ldx, void* dx, int lddx, int M, int C, const float* mean,
-                          const float* invstd, const float* gamma, const float* beta,
-                          const float* dgamma, const float* dbeta, int relu, hipStream_t st);
 
 // finalize-free variants: statistics accumulated in R replicas of [2][C] (fp32 atomics).
 // Blocks tile (row split) x (channel group) so each block only reduces its group's replicas.

@@ -305,8 +305,15 @@ def test_conv_wgrad_split_k_large_reduction():
 @pytest.mark.parametrize("C", [64, 256, 80, 2048])
 @pytest.mark.parametrize("relu,residual", [(True, False), (True, True), (False, False)])
 def test_bn_fwd_bwd(C, relu, residual):
+    """The path BNReLU trains with -- bn_stats_acc into R = 8 zeroed replicas, bn_forward_acc, then
+    bn_backward_acc through a zeroed backward accumulator -- against the PyTorch reference on the CPU.
+    Both sides read the same bf16-rounded z; the GPU's moments are 196-term fp32 sums (atomics over
+    the replicas) of a single-pass variance without cancellation (mean 1, std 3): an fp32 emulation of
+    those sums on the CPU (same seed, any summation order) is within 6e-8 of the reference mean and
+    running mean and 2.1e-7 of its invstd and running variance (relative), far inside the 1e-4 bounds
+    (profiles/bn_one_path.txt)."""
     torch.manual_seed(6)
-    N, H = 4, 7
+    N, H, R = 4, 7, 8
     z = bf(torch.randn(N, H, H, C, device=DEV) * 3 + 1)
     gamma = torch.rand(C, device=DEV) + 0.5
     beta = torch.randn(C, device=DEV) * 0.1
@@ -314,7 +321,10 @@ def test_bn_fwd_bwd(C, relu, residual):
     rm = torch.zeros(C, device=DEV)
     rv = torch.ones(C, device=DEV)
     y = torch.empty_like(z)
-    saved = Fn.bn_forward(z, gamma, beta, rm, rv, 0.9, 1e-5, y, relu, residual=res)
+    acc_f = torch.zeros(R, 2, C, device=DEV)
+    Fn.bn_stats_acc(z, acc_f, R)
+    saved = Fn.bn_forward_acc(z, gamma, beta, rm, rv, 0.9, 1e-5, y, relu, acc_f, R, torch.empty(C, device=DEV),
+                              torch.empty(C, device=DEV), residual=res)
     zc, gc, bc = z.float().cpu(), gamma.cpu(), beta.cpu()
     rmc, rvc = torch.zeros(C), torch.ones(C)
     yc = torch.empty(N, H, H, C)
@@ -328,12 +338,25 @@ def test_bn_fwd_bwd(C, relu, residual):
     gres = torch.empty_like(z)
     dg = torch.empty(C, device=DEV)
     db = torch.empty(C, device=DEV)
-    Fn.bn_backward(dy, y, z, saved, gamma, beta, mode, dg, db, dz, gres)
+    Fn.bn_backward_acc(dy, y, z, saved, gamma, beta, mode, dg, db, dz, torch.zeros(R, 2, C, device=DEV), R, gres)
     dzc, gresc, dgc, dbc = torch.empty(N, H, H, C), torch.empty(N, H, H, C), torch.empty(C), torch.empty(C)
     Fn.bn_backward(dy.float().cpu(), y.float().cpu(), zc, sc, gc, bc, mode, dgc, dbc, dzc, gresc)
     assert rel_err(db, dbc) < 1e-2 and rel_err(dg, dgc) < 1e-2
     assert rel_err(dz, dzc) < 2e-2
     assert rel_err(gres, gresc) < 1e-2
+
+
+def test_bn_reference_entry_points_reject_native_tensors():
+    """Fn.bn_forward / Fn.bn_backward are the PyTorch reference path: a native tensor (one the HIP
+    kernels own) must go through the _acc forms, and handing it to them is an error, not a fall-back."""
+    C = 64
+    z = torch.zeros(2, 3, 3, C, dtype=torch.bfloat16, device=DEV)
+    assert Fn.native(z)
+    v = torch.ones(C, device=DEV)
+    with pytest.raises(AssertionError, match="bn_stats_acc.*bn_forward_acc"):
+        Fn.bn_forward(z, v, v, v.clone(), v.clone(), 0.9, 1e-5, torch.empty_like(z), True)
+    with pytest.raises(AssertionError, match="bn_backward_acc"):
+        Fn.bn_backward(z, z, z, Fn.BNSaved(v, v), v, v, 0, v.clone(), v.clone(), torch.empty_like(z))
 
 
 @pytest.mark.parametrize("kind", ["max3s2same", "avg3s1same", "max3s2valid", "avg8valid", "max3s1same",
