@@ -6,7 +6,9 @@ synthetic ImageNet -> broadcast variables from rank 0 -> ``num_warmup_batches`` 
 -> ``num_batches`` timed steps logging ``Step / Img/sec / total_loss`` every
 ``display_every`` steps in the tf_cnn_benchmarks format -> ``total images/sec``.
 Plus: machine-readable JSON summary, checkpoint/resume (``--train_dir``), ``--trace_file``,
-fault injection and the HOROVOD_* environment knobs.
+fault injection and the HOROVOD_* environment knobs. ``--eval`` (``run_eval``) restores the latest
+checkpoint and reports ``Accuracy @ 1 / @ 5`` over the validation split instead of training;
+``--eval_during_training_every_n_steps`` runs the same pass inside a training run, untimed.
 """
 from __future__ import annotations
 
@@ -142,6 +144,18 @@ class BenchmarkCNN:
         from ..trainer import OPT_DEFAULTS, Trainer
 
         p = self.params
+        use_graph = bool(p.use_hip_graph) and self.on_gpu and p.horovod_device != "cpu"
+        self.evaluator = None
+        if p.eval:
+            # --eval: no Trainer (no optimizer owns the store: checkpoint.restore_latest loads the
+            # weights of any optimizer's checkpoint), no reducer -- the only collective is the
+            # final sum of the three counters
+            from ..trainer import Evaluator
+
+            self.trainer = self.reducer = None
+            self.opt_args = {}
+            self.evaluator = Evaluator(self.model, self.batch_size, use_graph=use_graph)
+            return
         reducer = None
         comp = None if p.gradient_compression == "none" else p.gradient_compression
         if self.size > 1:
@@ -157,7 +171,7 @@ class BenchmarkCNN:
                                optimizer=p.optimizer,
                                opt_args=self.opt_args if OPT_DEFAULTS[p.optimizer] else None,
                                weight_decay=p.weight_decay, reducer=reducer, world_size=self.size,
-                               use_graph=bool(p.use_hip_graph) and self.on_gpu and p.horovod_device != "cpu",
+                               use_graph=use_graph,
                                forward_only=bool(p.forward_only), label_smoothing=p.label_smoothing,
                                # --use_fp16: loss scaling as in the reference flags (static scale or
                                # automatic scaling), whichever 16-bit type computes
@@ -167,6 +181,12 @@ class BenchmarkCNN:
                                comm_check=True if p.comm_check else None)
         if p.horovod_device == "cpu" and self.size > 1 and self.on_gpu:
             self.trainer.reducer = _HostStagedReducer(reducer)
+        if p.eval_during_training_every_n_steps and not p.forward_only:
+            # in-training evaluation: a second captured graph on the same model, beside the
+            # training graph (the evaluator puts the model back into training mode)
+            from ..trainer import Evaluator
+
+            self.evaluator = Evaluator(self.model, self.batch_size, use_graph=use_graph, trainer=self.trainer)
 
     # ------------------------------------------------------------------ info
     def print_info(self):
@@ -177,18 +197,22 @@ class BenchmarkCNN:
         log_fn(f"Framework:   azure_hc_intel_tf_amd (PyTorch {torch.__version__}, HIP {torch.version.hip})")
         log_fn(f"Model:       {self.model_name}")
         log_fn(f"Dataset:     imagenet ({'TFRecords ' + p.data_dir if p.data_dir else 'synthetic'})")
-        log_fn(f"Mode:        {'forward-only' if p.forward_only else 'training'}")
+        log_fn(f"Mode:        {'evaluation' if p.eval else 'forward-only' if p.forward_only else 'training'}")
         log_fn(f"SingleSess:  False")
         log_fn(f"Batch size:  {self.batch_size * self.size} global")
         log_fn(f"             {self.batch_size} per device")
-        log_fn(f"Num batches: {self.num_batches}")
-        log_fn(f"Num epochs:  {self.num_batches * self.batch_size * self.size / 1281167:.2f}")
+        if self._one_pass():
+            log_fn("Num batches: one pass over the validation split")
+        else:
+            log_fn(f"Num batches: {self.num_batches}")
+            log_fn(f"Num epochs:  {self.num_batches * self.batch_size * self.size / 1281167:.2f}")
         log_fn(f"Devices:     {dev}")
         log_fn(f"NUMA bind:   False")
         log_fn(f"Data format: {p.data_format} (logical; NHWC kernels)")
         log_fn(f"Precision:   {self.compute_dtype}" + (" (HIP kernels)" if self.model.native else
                                                        " (PyTorch/MIOpen path)" if self.on_gpu else " (CPU)"))
-        log_fn(f"Optimizer:   {p.optimizer}" + "".join(f" {k}={v:g}" for k, v in self.opt_args.items()))
+        if not p.eval:
+            log_fn(f"Optimizer:   {p.optimizer}" + "".join(f" {k}={v:g}" for k, v in self.opt_args.items()))
         log_fn(f"Variables:   {p.variable_update}")
         log_fn(f"Workers:     {self.size} (one process per {'MI355X' if self.on_gpu else 'CPU worker'})")
         log_fn(f"Params:      {self.model.num_params():,} in {self.model.ps.num_tensors()} tensors")
@@ -200,23 +224,223 @@ class BenchmarkCNN:
         log_fn("==========")
 
     # ------------------------------------------------------------------ run
+    def _one_pass(self) -> bool:
+        """--eval on real data with neither --num_batches nor --num_epochs given: the validation
+        split is read exactly once, each rank stopping when its share is exhausted."""
+        p = self.params
+        return bool(p.eval and p.data_dir and not p._num_batches_given)
+
+    def _loader(self, train: bool, loop: bool = True):
+        from ..data.imagenet import ImageNetLoader
+
+        p = self.params
+        return ImageNetLoader(p.data_dir, self.batch_size, self.model.image_size, self.model.image_channels,
+                              self.device, rank=self.rank, world=self.size, train=train, loop=loop,
+                              seed=p.tf_random_seed, reader_threads=p.datasets_num_private_threads or 4,
+                              decode_threads=p.num_decode_threads or 8)
+
+    def _sum_over_ranks(self, counts):
+        """(examples, top-1 hits, top-5 hits) summed over the workers."""
+        if self.size > 1:
+            t = torch.tensor(list(counts), dtype=torch.int64, device=self.device if self.on_gpu else "cpu")
+            torch.distributed.all_reduce(t)
+            counts = t.tolist()
+        return tuple(int(c) for c in counts)
+
+    def _eval_pass(self, step: int):
+        """One in-training evaluation pass (--eval_during_training_every_n_steps): the validation
+        split (a second, one-pass loader) or ``num_eval_batches`` batches through the Evaluator;
+        logs one accuracy line with the step number and returns the top-1 accuracy."""
+        from ..trainer import synthetic_batch
+
+        p = self.params
+        ev = self.evaluator
+        if self._eval_bufs is None:  # the evaluator's own static inputs (the training batch stays)
+            self._eval_bufs = synthetic_batch(self.model, self.batch_size, seed=p.tf_random_seed + 7919 + self.rank)
+        images, labels = self._eval_bufs
+        ev.reset()
+        if p.data_dir:
+            loader = self._loader(train=False, loop=False)
+            try:
+                n = 0
+                while (p.num_eval_batches is None or n < p.num_eval_batches) and loader.next_into(images, labels):
+                    ev.step(images, labels)
+                    n += 1
+            finally:
+                loader.close()
+        else:
+            for _ in range(10 if p.num_eval_batches is None else p.num_eval_batches):
+                ev.step(images, labels)
+        ex, t1, t5 = self._sum_over_ranks(ev.result())
+        top1, top5 = t1 / max(ex, 1), t5 / max(ex, 1)
+        if self.rank == 0:
+            log_fn("Step %d: Accuracy @ 1 = %.4f Accuracy @ 5 = %.4f [%d examples]" % (step, top1, top5, ex))
+        self.eval_history.append({"step": step, "top_1_accuracy": top1, "top_5_accuracy": top5, "examples": ex})
+        return top1
+
+    def run_eval(self):
+        """--eval: restore the latest checkpoint (or keep the seeded initial weights), run the
+        validation data through the Evaluator and report top-1 / top-5 accuracy. The display lines
+        keep the training format with 0.000 in the loss column (no loss is computed)."""
+        from ..trainer import synthetic_batch
+        from ..utils import checkpoint
+
+        p = self.params
+        hvd = self.hvd
+        ev = self.evaluator
+        images, labels = synthetic_batch(self.model, self.batch_size, seed=p.tf_random_seed + self.rank)
+        one_pass = self._one_pass()
+        loader = None
+        if p.data_dir:
+            loader = self._loader(train=False, loop=not one_pass)
+            if self.rank == 0:
+                log_fn(f"Reading {len(loader.files)} TFRecord shards from {p.data_dir}")
+        self.loader = loader
+        ckpt_step = None
+        if p.train_dir:
+            step, err = 0, None
+            if self.rank == 0:
+                if checkpoint.latest(p.train_dir) is None:
+                    err = f"--eval: no checkpoint in --train_dir={p.train_dir}"
+                else:
+                    step = checkpoint.restore_latest(p.train_dir, self.model.ps)
+            if self.size > 1:
+                step, err = hvd.broadcast_object((step, err), 0)
+            if err is not None:
+                if loader is not None:
+                    loader.close()
+                raise FileNotFoundError(err)
+            ckpt_step = int(step)
+            if self.rank == 0:
+                log_fn(f"Restored checkpoint at step {ckpt_step} from {p.train_dir}")
+        elif self.rank == 0:
+            log_fn("No --train_dir: evaluating the seeded initial weights")
+        if self.size > 1:
+            hvd.broadcast_global_variables(self.model, 0)
+        sync = torch.cuda.synchronize if self.on_gpu else (lambda: None)
+
+        log_fn("Running warm up") if self.rank == 0 else None
+        for _ in range(self.num_warmup_batches):
+            # (a one-pass run warms up on the synthetic batch: the split is read exactly once)
+            if loader is not None and not one_pass:
+                loader.next_into(images, labels)
+            ev.step(images, labels)
+        sync()
+        hvd.barrier()
+        log_fn("Done warm up") if self.rank == 0 else None
+        if p.trace_file:
+            from ..utils.tracing import trace_step
+
+            trace_step(lambda: ev._body(images, labels), p.trace_file, on_gpu=self.on_gpu)
+        ev.reset()
+
+        if self.rank == 0:
+            log_fn("Step\tImg/sec\ttotal_loss")
+        step_times: List[float] = []
+        evs = []
+        sync()
+        t_start = time.perf_counter()
+        t_prev = t_start
+        if self.on_gpu:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            evs.append(e0)
+
+        def drain():
+            evs[-1].synchronize()
+            while len(step_times) < len(evs) - 1:
+                k = len(step_times)
+                step_times.append(evs[k].elapsed_time(evs[k + 1]) / 1000.0)
+
+        step = 0
+        while one_pass or step < self.num_batches:
+            if loader is not None and not loader.next_into(images, labels):
+                break  # (one pass: this rank's share is exhausted)
+            ev.step(images, labels)
+            step += 1
+            if self.on_gpu:
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                evs.append(e)
+            else:
+                now = time.perf_counter()
+                step_times.append(now - t_prev)
+                t_prev = now
+            if step == 1 or step % p.display_every == 0 or (not one_pass and step == self.num_batches):
+                if self.on_gpu:
+                    drain()
+                if self.rank == 0:
+                    log_fn("%i\t%s\t%.3f" % (step, get_perf_timing_str(self.batch_size, step_times), 0.0))
+        sync()
+        elapsed = time.perf_counter() - t_start
+        if self.on_gpu and len(evs) > 1:
+            drain()
+        elapsed_max = elapsed
+        if self.size > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=self.device if self.on_gpu else "cpu")
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            elapsed_max = float(t.item())
+        if loader is not None:
+            loader.close()
+        own = ev.result()
+        ex, t1, t5 = self._sum_over_ranks(own)
+        top1, top5 = t1 / max(ex, 1), t5 / max(ex, 1)
+        # images pushed through the model (a padded last batch counts its real rows only)
+        n_img = ex if one_pass else self.size * self.batch_size * step
+        images_per_sec = n_img / max(elapsed_max, 1e-9)
+        own_images_per_sec = (own[0] if one_pass else self.size * self.batch_size * step) / max(elapsed, 1e-9)
+        if self.rank == 0:
+            log_fn("Accuracy @ 1 = %.4f Accuracy @ 5 = %.4f [%d examples]" % (top1, top5, ex))
+            log_fn("-" * 64)
+            log_fn("total images/sec: %.2f" % images_per_sec)
+            log_fn("-" * 64)
+        else:
+            log_fn("[rank %d] total images/sec: %.2f" % (self.rank, own_images_per_sec))
+        summary = {
+            "model": self.model_name, "device": "MI355X" if self.on_gpu else platform.processor() or "cpu",
+            "mode": "evaluation", "workers": self.size, "batch_size_per_worker": self.batch_size,
+            "global_batch": self.batch_size * self.size, "num_batches": step,
+            "num_warmup_batches": self.num_warmup_batches, "total_images_per_sec": images_per_sec,
+            "elapsed_s": elapsed_max, "final_loss": None,
+            "step_time_ms": {"mean": 1000 * float(np.mean(step_times)) if step_times else None,
+                             "p50": 1000 * float(np.percentile(step_times, 50)) if step_times else None,
+                             "p90": 1000 * float(np.percentile(step_times, 90)) if step_times else None},
+            "dtype": self.compute_dtype, "data": "imagenet-tfrecord" if loader else "synthetic",
+            "input_decode_s": loader.decode_s if loader else None,
+            "variable_update": p.variable_update, "hip_graph": ev.use_graph,
+            "eval": {"top_1_accuracy": top1, "top_5_accuracy": top5, "examples": ex, "checkpoint_step": ckpt_step},
+        }
+        self.summary = summary
+        self._write_summary(summary)
+        return summary
+
+    def _write_summary(self, summary):
+        p = self.params
+        if self.rank != 0:
+            return
+        out = p.json_summary
+        if not out and p.benchmark_log_dir:
+            os.makedirs(p.benchmark_log_dir, exist_ok=True)
+            out = os.path.join(p.benchmark_log_dir, "summary.json")
+        if out:
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(summary, f, indent=1)
+
     def run(self):
         from ..trainer import synthetic_batch
         from ..utils import checkpoint
 
         p = self.params
+        if p.eval:
+            return self.run_eval()
         hvd = self.hvd
         images, labels = synthetic_batch(self.model, self.batch_size, seed=p.tf_random_seed + self.rank)
         loader = None
         if p.data_dir:
             # real ImageNet TFRecords: each step's batch is written in place into the static
             # (graph-captured) input buffers by the native prefetch + GPU preprocess pipeline
-            from ..data.imagenet import ImageNetLoader
-
-            loader = ImageNetLoader(p.data_dir, self.batch_size, self.model.image_size, self.model.image_channels,
-                                    self.device, rank=self.rank, world=self.size, train=not p.forward_only,
-                                    seed=p.tf_random_seed, reader_threads=p.datasets_num_private_threads or 4,
-                                    decode_threads=p.num_decode_threads or 8)
+            loader = self._loader(train=not p.forward_only)
             if self.rank == 0:
                 log_fn(f"Reading {len(loader.files)} TFRecord shards from {p.data_dir}")
         self.loader = loader
@@ -261,6 +485,13 @@ class BenchmarkCNN:
         use_events = self.on_gpu
         evs = []
         last_save = time.time()
+        # in-training evaluation: a pass after every N-th timed step, outside the timing (the next
+        # step's interval starts at an event recorded after the pass; its wall time leaves elapsed)
+        eval_every = int(p.eval_during_training_every_n_steps or 0) if self.evaluator is not None else 0
+        restarts = {}
+        eval_s = 0.0
+        self._eval_bufs = None
+        self.eval_history = []
         sync()
         t_start = time.perf_counter()
         t_prev = t_start
@@ -289,7 +520,7 @@ class BenchmarkCNN:
                     evs[-1].synchronize()
                     while len(step_times) < len(evs) - 1:
                         k = len(step_times)
-                        step_times.append(evs[k].elapsed_time(evs[k + 1]) / 1000.0)
+                        step_times.append(restarts.get(k, evs[k]).elapsed_time(evs[k + 1]) / 1000.0)
                 if self.rank == 0:
                     line = "%i\t%s\t%.3f" % (step, get_perf_timing_str(self.batch_size, step_times), loss)
                     if acc:
@@ -305,12 +536,28 @@ class BenchmarkCNN:
                 if due:
                     checkpoint.save(p.train_dir, gstep, self.model.ps)
                     last_save = time.time()
+            if eval_every and step % eval_every == 0:
+                sync()
+                t0 = time.perf_counter()
+                top1 = self._eval_pass(step)
+                sync()
+                t_prev = time.perf_counter()
+                eval_s += t_prev - t0
+                if use_events:
+                    e = torch.cuda.Event(enable_timing=True)
+                    e.record()
+                    restarts[len(evs) - 1] = e
+                if p.stop_at_top_1_accuracy is not None and top1 >= p.stop_at_top_1_accuracy:
+                    if self.rank == 0:
+                        log_fn(f"Stopping at step {step}: top-1 accuracy {top1:.4f} >= {p.stop_at_top_1_accuracy:g}")
+                    self.num_batches = step  # (the same decision on every rank: the counts are summed)
+                    break
         sync()
-        elapsed = time.perf_counter() - t_start
+        elapsed = time.perf_counter() - t_start - eval_s
         if use_events:
             while len(step_times) < len(evs) - 1:
                 k = len(step_times)
-                step_times.append(evs[k].elapsed_time(evs[k + 1]) / 1000.0)
+                step_times.append(restarts.get(k, evs[k]).elapsed_time(evs[k + 1]) / 1000.0)
         elapsed_max = elapsed
         if self.size > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=self.device if self.on_gpu else "cpu")
@@ -362,6 +609,8 @@ class BenchmarkCNN:
             "comm": comm,
             "optimizer": p.optimizer, "optimizer_args": dict(self.opt_args),
         }
+        if eval_every:
+            summary["eval_during_training"] = self.eval_history
         if self.size > 1:
             per_rank = torch.tensor([own_images_per_sec], dtype=torch.float64,
                                     device=self.device if self.on_gpu else "cpu")
@@ -372,15 +621,7 @@ class BenchmarkCNN:
             t1, t5 = accs
             summary["top_1_accuracy"], summary["top_5_accuracy"] = float(t1), float(t5)
         self.summary = summary
-        if self.rank == 0:
-            out = p.json_summary
-            if not out and p.benchmark_log_dir:
-                os.makedirs(p.benchmark_log_dir, exist_ok=True)
-                out = os.path.join(p.benchmark_log_dir, "summary.json")
-            if out:
-                os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-                with open(out, "w") as f:
-                    json.dump(summary, f, indent=1)
+        self._write_summary(summary)
         return summary
 
     def _maybe_fault(self, step: int):

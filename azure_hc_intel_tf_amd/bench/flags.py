@@ -44,7 +44,8 @@ FLAGS: List[Flag] = [
     # --- the reference's flag set (run-tf-sing-ucx-openmpi.sh:62-81)
     Flag("batch_size", 0, int, "per-device (per-worker) batch size; 0 = model default"),
     Flag("num_warmup_batches", None, int, "untimed warmup steps (default: model/device dependent)"),
-    Flag("num_batches", 100, int, "timed steps"),
+    Flag("num_batches", None, int, "timed steps (default 100; with --eval on real data and neither this nor "
+         "--num_epochs given: one pass over the validation split)"),
     Flag("model", "trivial", str, "model name: resnet50|101|152[_v1.5], inception3, vgg11|16|19, alexnet, googlenet, "
          "overfeat, lenet, trivial"),
     Flag("num_intra_threads", 0, int, "host intra-op threads (CPU path: torch.set_num_threads)"),
@@ -58,6 +59,16 @@ FLAGS: List[Flag] = [
     Flag("optimizer", "sgd", str, "sgd | momentum | rmsprop | adam", choices=list(OPT_DEFAULTS)),
     Flag("forward_only", False, parse_bool, "inference-only benchmark (BN from the moving statistics, applied with "
          "the residual add and ReLU in the conv GEMM's epilogue; HCB_FUSE_INFER_BN=0: separate BN passes)"),
+    Flag("eval", False, parse_bool, "evaluate instead of training: restore the latest checkpoint of --train_dir "
+         "(without one: the seeded initial weights), run the validation split through the model in inference "
+         "mode and print 'Accuracy @ 1 = ... Accuracy @ 5 = ... [N examples]' (top-1 / top-5 counted on the "
+         "device by the eval_metrics kernel); never writes to --train_dir; not with --forward_only"),
+    Flag("eval_during_training_every_n_steps", 0, int, "training: run an evaluation pass after every N-th timed "
+         "step (0 = off); its time is excluded from the step times and from total images/sec"),
+    Flag("num_eval_batches", None, int, "batches of an in-training evaluation pass (default: the whole validation "
+         "split with --data_dir, 10 on synthetic data)"),
+    Flag("stop_at_top_1_accuracy", None, float, "end training (the final checkpoint is still written) once an "
+         "in-training evaluation pass reaches this top-1 accuracy"),
     Flag("device", "gpu", str, "gpu (MI355X) or cpu", choices=["gpu", "cpu"]),
     Flag("mkl", False, parse_bool, "TF-MKL switch", noop_on_gpu=True),
     Flag("variable_update", "horovod", str, "horovod (RCCL data parallel) | replicated (single process)",
@@ -166,6 +177,12 @@ def parse_flags(argv: Optional[List[str]] = None, allow_unknown: bool = True) ->
     ns, unknown = ap.parse_known_args(_normalise(argv))
     p = Params(vars(ns))
     p["_unknown"] = unknown
+    if p["eval"] and p["forward_only"]:
+        raise ValueError("--eval and --forward_only are mutually exclusive (evaluation is its own mode)")
+    # whether the length of the run was asked for: --eval on real data reads the split once if not
+    p["_num_batches_given"] = p["num_batches"] is not None or p["num_epochs"] is not None
+    if p["num_batches"] is None:
+        p["num_batches"] = 100
     if unknown and not allow_unknown:
         ap.error(f"unrecognized flags: {unknown}")
     return p

@@ -18,7 +18,8 @@ per MI355X:
 A background thread keeps ``depth`` batches in flight, so host decode overlaps the GPU step;
 with fewer CPU cores than the GPU can consume, the run is input-bound and the log says so
 (the headline benchmark uses synthetic data, as BASELINE.json specifies).
-Eval mode (``train=False``) uses the 87.5 % central crop without flips.
+Eval mode (``train=False``) uses the 87.5 % central crop without flips; ``loop=False`` reads the
+split exactly once (``--eval``), padding the short last batch with label -1 rows.
 Normalisation x/127.5 - 1 is this engine's convention (parity with the TF build unpinned).
 """
 from __future__ import annotations
@@ -101,13 +102,22 @@ def preprocess_reference(crops: List[np.ndarray], flips: List[int], out: torch.T
     return out
 
 
+_END = object()  # producer -> consumer: a loop=False pass is exhausted
+
+
 class ImageNetLoader:
     """Fills a model's static (images, labels) buffers with the next real batch."""
 
     def __init__(self, data_dir: str, batch_size: int, image_size: int, channels: int, device,
                  rank: int = 0, world: int = 1, train: bool = True, seed: int = 0, reader_threads: int = 4,
-                 decode_threads: int = 8, depth: int = 3, shuffle_buffer: int = 4096, subset: Optional[str] = None):
+                 decode_threads: int = 8, depth: int = 3, shuffle_buffer: int = 4096, subset: Optional[str] = None,
+                 loop: bool = True):
         self.B = batch_size
+        # loop=False: ONE pass over this rank's share of the split (evaluation): a short last batch
+        # is padded (label -1, an already-decoded image repeated) and next_into returns the number
+        # of real rows, 0 once the data is exhausted
+        self.loop = loop
+        self._exhausted = False
         self.S = image_size
         self.C = channels
         self.device = torch.device(device)
@@ -124,7 +134,7 @@ class ImageNetLoader:
         self.max_side = 4 * image_size
         self.pf = native().Prefetcher(self.files, rank=rank, world=world, threads=reader_threads,
                                       shuffle_buffer=shuffle_buffer if train else 1, capacity=max(8192, shuffle_buffer),
-                                      seed=seed, train=train, loop=True)
+                                      seed=seed, train=train, loop=loop)
         self.pool = ThreadPoolExecutor(max_workers=decode_threads, thread_name_prefix="hcb-decode")
         cap = batch_size * self.max_side * self.max_side * 3
         pin = self.device.type == "cuda"
@@ -155,8 +165,13 @@ class ImageNetLoader:
                     ev.synchronize()  # the previous H2D copy out of this slot has finished
                 t0 = time.perf_counter()
                 samples = self.pf.next(self.B)
-                if len(samples) < self.B:
-                    raise RuntimeError("input pipeline ran dry")
+                real = len(samples)
+                if real < self.B:
+                    if self.loop:
+                        raise RuntimeError("input pipeline ran dry")
+                    if real == 0:  # one pass done: the consumer returns 0 from here on
+                        self.ready.put(_END)
+                        return
                 crops = list(self.pool.map(
                     lambda s: decode_crop(s[0], s[2], s[4], self.S, self.max_side), samples))
                 buf = self.slots[slot].numpy()
@@ -167,23 +182,33 @@ class ImageNetLoader:
                     buf[off:off + n] = c.reshape(-1)
                     desc[i] = (off, c.shape[0], c.shape[1], s[3])
                     off += (n + 15) // 16 * 16
-                labels = np.array([s[1] for s in samples], dtype=np.int64)
+                desc[real:] = desc[0]  # padding rows of a short last batch: the first image again
+                crops += [crops[0]] * (self.B - real)
+                labels = np.full(self.B, -1, dtype=np.int64)
+                labels[:real] = [s[1] for s in samples]
                 self.decode_s += time.perf_counter() - t0
-                self.ready.put((slot, desc, labels, crops if self.device.type != "cuda" else None))
+                self.ready.put((slot, desc, labels, crops if self.device.type != "cuda" else None, real))
         except Exception as e:  # surfaced on the consumer side
             self._err = e
             self.ready.put(None)
 
     # ---------------------------------------------------------------- consumer
-    def next_into(self, images: torch.Tensor, labels: torch.Tensor) -> None:
+    def next_into(self, images: torch.Tensor, labels: torch.Tensor) -> int:
         """Write the next batch into ``images`` [B, S, S, C] / ``labels`` [B] in place (stream
-        ordered on the current stream, so a following graph replay sees it)."""
+        ordered on the current stream, so a following graph replay sees it). Returns the number of
+        real rows: the batch size, or with ``loop=False`` fewer for the padded last batch (its
+        padding rows carry label -1) and 0, with the buffers untouched, once the data is exhausted."""
+        if self._exhausted:
+            return 0
         item = self.ready.get()
         if item is None:
             raise RuntimeError(f"input pipeline failed: {self._err!r}")
-        slot, desc, lab, crops = item
+        if item is _END:
+            self._exhausted = True
+            return 0
+        slot, desc, lab, crops, real = item
         if self.device.type == "cuda":
-            nbytes = int(desc[-1, 0] + desc[-1, 1] * desc[-1, 2] * 3)
+            nbytes = int(desc[real - 1, 0] + desc[real - 1, 1] * desc[real - 1, 2] * 3)
             self.dev_stage[:nbytes].copy_(self.slots[slot][:nbytes], non_blocking=True)
             desc_t = torch.from_numpy(desc)
             self.dev_desc.copy_(desc_t, non_blocking=True)
@@ -199,6 +224,7 @@ class ImageNetLoader:
             labels.copy_(torch.from_numpy(lab))
             self.free.put((slot, None))
         self.batches += 1
+        return real
 
     def close(self):
         self._stop = True

@@ -1278,6 +1278,30 @@ def softmax_xent(logits, labels, ncls, row_loss, dlogits, scale, scale_dev=None,
     dlogits[:, :ncls].copy_(p * scale)
 
 
+def eval_metrics(logits, labels, ncls, counters):
+    """counters (int64 [3]) += (examples, top-1 hits, top-5 hits) of a batch of fp32 logits
+    [B, ld >= ncls] -- tf_cnn_benchmarks --eval's tf.nn.in_top_k: with t the target's logit, a row is
+    a top-k hit iff t is finite and fewer than k of its ``ncls`` classes are strictly greater than
+    t (ties across the boundary count as inside, a NaN is never greater, a NaN / Inf target misses).
+    label < 0 marks a padding row (skipped, no example); label >= ncls is an example and a miss.
+    The GPU kernel adds into ``counters`` with integer atomics: one launch, nothing to zero, no
+    host read, capturable."""
+    if logits.is_cuda:  # the fp32 logits: same kernel in every compute mode
+        _ext.ops().eval_metrics(logits, ld(logits), labels, ncls, counters)
+        return
+    lab = labels.view(-1).long()
+    lg = logits.view(lab.numel(), -1)[:, :ncls].float()
+    real = lab >= 0
+    ok = real & (lab < ncls)
+    t = lg.gather(1, lab.clamp(0, ncls - 1).view(-1, 1))
+    above = (lg > t).sum(1)
+    ok &= torch.isfinite(t.view(-1))
+    c = counters.view(-1)
+    c[0] += int(real.sum())
+    c[1] += int((ok & (above < 1)).sum())
+    c[2] += int((ok & (above < 5)).sum())
+
+
 def add(a, b, out=None):
     """out = a + b on activations (bf16 HIP kernel on the GPU)."""
     out = torch.empty_like(a) if out is None else out

@@ -561,6 +561,100 @@ class Trainer:
                 "fusion_threshold_bytes": getattr(self.reducer, "bucket_bytes", None)}
 
 
+class Evaluator:
+    """Top-1 / top-5 accuracy of a model over a stream of batches (tf_cnn_benchmarks ``--eval``
+    and ``--eval_during_training_every_n_steps``), counted on the device.
+
+    One step is: clear the statistics scratch -> masters to GEMM operands -> inference forward
+    (moving-statistics BN, no dropout) -> ``Fn.eval_metrics`` adding the batch's examples and
+    hits into ``counters`` (int64 [3]) -> release the activations. No loss kernel, no dlogits, no
+    optimizer, and no host read: on the GPU the step is ONE captured graph (its own, beside the
+    training graph when there is one) whose replays keep accumulating; ``result()`` is the only
+    synchronising read. Models on the PyTorch path and on the CPU run the same step eagerly.
+
+    An eval pass writes only per-step scratch (the statistics buffer the next training step
+    clears, the GEMM operands it regenerates) and its own counters and logits: masters, optimizer
+    slots, BN moving statistics and shifts, the dropout step counter and the loss-scale state are
+    not touched. Built beside a ``Trainer`` (``trainer=``), it puts the model back into training
+    mode after every step that ran the layers' Python (eager or capture)."""
+
+    def __init__(self, model, batch_size: int, use_graph: bool = True, graph_warmup: int = 1, trainer=None):
+        self.model = model
+        self.ps = model.ps
+        self.B = batch_size
+        self.dev = model.device
+        self.trainer = trainer
+        self.use_graph = use_graph and self.dev.type == "cuda" and getattr(model, "native", True)
+        self.graph_warmup = graph_warmup
+        self.counters = torch.zeros(3, dtype=torch.int64, device=self.dev)
+        self.logits = None
+        self.steps_done = 0
+        self._g = None
+        self._static = None
+        if trainer is None and hasattr(model, "set_training"):
+            model.set_training(False)
+
+    def _body(self, images, labels):
+        if hasattr(self.model, "activate"):
+            self.model.activate()
+        ps = self.ps
+        if ps.statbuf.is_cuda and ps.statbuf.numel() % 4 == 0:
+            Fn.zero_bufs([ps.statbuf])
+        else:
+            ps.zero_stats()
+        ps.repack()
+        with range_("forward"):
+            logits = self.model.forward(images)
+        self.logits = logits
+        Fn.eval_metrics(logits, labels, self.model.num_classes, self.counters)
+        self.model.clear()
+
+    def _in_eval_mode(self, fn, images, labels):
+        """Run ``fn`` with the model in inference mode; beside a Trainer, training mode after."""
+        if self.trainer is None or not hasattr(self.model, "set_training"):
+            return fn(images, labels)
+        self.model.set_training(False)
+        try:
+            return fn(images, labels)
+        finally:
+            self.model.set_training(True)
+
+    def _capture(self, images, labels):
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        # thread_local: an input pipeline's thread may wait on its copy events meanwhile
+        with torch.cuda.graph(g, pool=torch.cuda.graph_pool_handle(), capture_error_mode="thread_local"):
+            self._body(images, labels)
+        self._g = g
+        self._static = (images, labels)
+        torch.cuda.synchronize()
+
+    def reset(self):
+        """Zero the counters (outside the graph)."""
+        self.counters.zero_()
+
+    def step(self, images, labels):
+        """Count one batch (labels < 0: padding rows of a partial last batch)."""
+        with range_("eval_step"):
+            if not self.use_graph:
+                self._in_eval_mode(self._body, images, labels)
+            else:
+                if self._static is not None and (images is not self._static[0] or labels is not self._static[1]):
+                    raise ValueError("graph-captured evaluator needs the same (static) input buffers every step")
+                if self._g is None and self.steps_done < self.graph_warmup:
+                    self._in_eval_mode(self._body, images, labels)
+                else:
+                    if self._g is None:
+                        self._in_eval_mode(self._capture, images, labels)
+                    self._g.replay()
+            self.steps_done += 1
+
+    def result(self):
+        """(examples, top-1 hits, top-5 hits) so far as Python ints: one synchronising read."""
+        ex, t1, t5 = self.counters.tolist()
+        return int(ex), int(t1), int(t5)
+
+
 def synthetic_batch(model, batch_size: int, seed: int = 0):
     """tf_cnn_benchmarks synthetic ImageNet: truncated-normal images (mean 127, sd 60) and
     uniform labels in [0, num_classes-1), created once and reused every step."""

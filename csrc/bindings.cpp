@@ -564,6 +564,27 @@ void softmax_xent(const Tensor& logits, int64_t ld, const Tensor& labels, int64_
                            (float)label_smoothing);
 }
 
+// counters[0:3] += {examples, top-1 hits, top-5 hits} of the batch (csrc/kernels/metrics.hip)
+void eval_metrics(const Tensor& logits, int64_t ld, const Tensor& labels, int64_t ncls, const Tensor& counters) {
+  check_f32(logits, "logits");
+  check_cuda(labels, "labels");
+  check_cuda(counters, "counters");
+  TORCH_CHECK(labels.scalar_type() == at::kLong, "hcb.eval_metrics: labels int64");
+  TORCH_CHECK(counters.scalar_type() == at::kLong, "hcb.eval_metrics: counters int64");
+  TORCH_CHECK(logits.is_contiguous() && labels.is_contiguous() && counters.is_contiguous(),
+              "hcb.eval_metrics: contiguous tensors only");
+  TORCH_CHECK(counters.numel() >= 3, "hcb.eval_metrics: counters[3]");
+  TORCH_CHECK(ncls >= 1 && ld >= ncls, "hcb.eval_metrics: ld >= ncls >= 1");
+  TORCH_CHECK(logits.device() == labels.device() && logits.device() == counters.device(),
+              "hcb.eval_metrics: logits, labels and counters on one device");
+  const int64_t B = labels.numel();
+  TORCH_CHECK(B * ld < (int64_t)1 << 31, "hcb.eval_metrics: B * ld < 2^31");
+  TORCH_CHECK(logits.numel() >= B * ld, "hcb.eval_metrics: logits hold ", logits.numel(), " elements, B * ld = ",
+              B * ld);
+  hcb::launch_eval_metrics(logits.data_ptr<float>(), (int)ld, labels.data_ptr<int64_t>(), (int)B, (int)ncls,
+                           counters.data_ptr<int64_t>(), cur_stream());
+}
+
 void nonfinite(const Tensor& g, const Tensor& flag) {
   check_f32(g, "g");
   check_f32(flag, "flag");
@@ -1308,6 +1329,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("gap_fwd(Tensor x, Tensor(a!) y, int N, int HW, int C) -> ()");
   m.def("gap_bwd(Tensor dy, Tensor(a!) dx, int N, int HW, int C) -> ()");
   m.def("softmax_xent(Tensor logits, int ld, Tensor labels, int ncls, Tensor(a!) row_loss, Tensor(b!) dlogits, int lddl, float scale, Tensor? scale_dev=None, Tensor(c!)? dl32=None, float label_smoothing=0.0) -> ()");
+  m.def("eval_metrics(Tensor logits, int ld, Tensor labels, int ncls, Tensor(a!) counters) -> ()");
   m.def("nonfinite(Tensor g, Tensor(a!) flag) -> ()");
   m.def("loss_total(Tensor row_loss, int B, Tensor? l2, float half_wd, Tensor(a!) loss) -> ()");
   m.def("loss_scale_update(Tensor(a!) hyper, float world, bool dynamic) -> ()");
@@ -1354,6 +1376,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("conv_igemm", conv_igemm);
   m.impl("conv_igemm_bnb", conv_igemm_bnb);
   m.impl("conv_igemm_inf", conv_igemm_inf);
+  m.impl("eval_metrics", eval_metrics);
   m.impl("nonfinite", nonfinite);
   m.impl("loss_total", loss_total);
   m.impl("loss_scale_update", loss_scale_update);

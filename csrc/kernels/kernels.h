@@ -213,6 +213,10 @@ void launch_softmax_xent(const float* logits, int ld, const int64_t* labels, int
                          float* row_loss, void* dlogits, int lddl, float scale, const float* scale_dev,
                          hipStream_t st, bool f32 = false, float* dl32 = nullptr,
                          float label_smoothing = 0.f);
+// metrics.hip: counters (device int64 [3]) += {examples, top-1 hits, top-5 hits} of the batch
+// (tf.nn.in_top_k; label < 0 rows are skipped); one launch, no zeroing, graph-capturable
+void launch_eval_metrics(const float* logits, int ld, const int64_t* labels, int B, int ncls, int64_t* counters,
+                         hipStream_t st);
 constexpr int ZERO_BUFS = 6;
 void launch_zero_bufs(float* const* ptrs, const int64_t* ns, int nb, hipStream_t st);
 void launch_colsum2(const void* g, int ld, int M, int N, int is_f32, float* out, hipStream_t st);

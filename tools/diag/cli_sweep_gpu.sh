@@ -36,6 +36,7 @@ if [ "${SET:-1}" = 3 ]; then  # third set: checkpoints across precisions, real d
   run ck_bf16_resume $R50 --train_dir=/tmp/hcb_cli_ckpt3 --optimizer=momentum --compute_dtype=bf16
   run ck_fp16_resume $R50 --train_dir=/tmp/hcb_cli_ckpt3 --optimizer=momentum --use_fp16=True
   run ck_fp32_fwd $R50 --train_dir=/tmp/hcb_cli_ckpt3 --forward_only=True
+  run ck_fp32_eval_data --model=resnet50 --batch_size=32 --num_warmup_batches=1 --train_dir=/tmp/hcb_cli_ckpt3 --eval --data_dir=$D --data_name=imagenet
   run ck_bs32_resume --model=resnet50 --batch_size=32 --num_batches=4 --num_warmup_batches=1 --train_dir=/tmp/hcb_cli_ckpt3 --optimizer=momentum
   for m in resnet50_v2 googlenet vgg16 alexnet; do
     run ${m}_data_fp32 --model=$m $SMALL --data_dir=$D --data_name=imagenet
@@ -71,6 +72,9 @@ run r50_default $R50
 run r50_forward_only $R50 --forward_only=True
 run r50_ckpt_save $R50 --train_dir=/tmp/hcb_cli_ckpt --save_model_steps=3 --optimizer=momentum
 run r50_ckpt_resume $R50 --train_dir=/tmp/hcb_cli_ckpt --save_model_steps=3 --optimizer=momentum
+run r50_eval_ckpt $R50 --eval --train_dir=/tmp/hcb_cli_ckpt
+run r50_eval_init_bf16 $R50 --eval --compute_dtype=bf16
+run r50_eval_in_training $R50 --optimizer=momentum --eval_during_training_every_n_steps=3 --num_eval_batches=2
 run r50_trace $R50 --trace_file=$OUT/trace.json
 run r50_accuracy_smoothing $R50 --print_training_accuracy=True --label_smoothing=0.1
 run r50_eager $R50 --use_hip_graph=False
