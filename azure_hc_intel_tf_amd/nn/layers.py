@@ -807,24 +807,14 @@ class Logits(Layer):
             Fn._ext.ops().colsum(self.dl32, self.ld, B, self.ncls, self.b.grad)
         else:
             Fn.colsum(dlogits, B, self.ncls, self.b.grad)
-        if Fn.native(x) and x.dtype == torch.float32:  # fp32 path: Planes operands (conv_p3.hip)
-            dlp = Fn.to_planes(dlogits)
-            Fn.conv_wgrad(dlp.view(B, 1, 1, self.ld), x.view(B, 1, 1, self.cin), self._wgrad_spec(),
-                          self.w.grad.view(self.ncls, self.cin))
-            dx = torch.empty((B, self.cin), dtype=torch.float32, device=x.device)
-            Fn.conv_dgrad(dlp.view(B, 1, 1, self.ld), self._dgrad_spec(), self.pack.tr, None,
-                          dx.view(B, 1, 1, self.cin), False)
-        elif Fn.native(x):
-            hcb = Fn._ext.ops()
-            geom = [B, 1, 1, self.cin, self.cin, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, self.ncls, self.ld]
-            cfg, splits = 2, 1
-            hcb.conv_wgrad(dlogits, x, self.w.grad.view(self.ncls, self.cin), geom, cfg, splits)
+        if Fn.native(x):  # 1x1 conv gradients over B pixels (fp32 path: Planes operands, conv_p3.hip)
+            p3 = x.dtype == torch.float32
+            dl = (Fn.to_planes(dlogits) if p3 else dlogits).view(B, 1, 1, self.ld)
+            Fn.conv_wgrad(dl, x.view(B, 1, 1, self.cin), self._wgrad_spec(), self.w.grad.view(self.ncls, self.cin),
+                          cfg=None if p3 else (2, 1))
             dx = torch.empty((B, self.cin), dtype=x.dtype, device=x.device)
-            C = self.ld
-            geom = [B, 1, 1, C, C, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 1, self.cin, C, self.pack.Kpad_t, self.cin,
-                    0, 1, 1, 1, 1, 0, Fn._f32o(dx)]
-            cfgd = Fn.conv_plan(B, self.cin, C)[0]
-            hcb.conv_igemm(dlogits, self.pack.tr, dx, None, None, None, geom, cfgd, None, None)
+            Fn.conv_dgrad(dl, self._dgrad_spec(), self.pack.tr, None, dx.view(B, 1, 1, self.cin), False,
+                          cfg=None if p3 else (Fn.conv_plan(B, self.cin, self.ld)[0], 1))
         else:
             g = dlogits[:, :self.ncls]
             self.w.grad.view(self.ncls, self.cin).add_((g.t() @ x).float())

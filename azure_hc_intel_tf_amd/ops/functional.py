@@ -18,6 +18,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -287,6 +288,124 @@ def same_pads(size: int, k: int, s: int, d: int = 1):
     return total // 2, total - total // 2
 
 
+# ----------------------------------------------------------------- GEMM geometry
+class ConvGeom(NamedTuple):
+    """A forward / data-gradient / inference conv GEMM as the ops receive it (``geom``, 33 ints). The
+    field order is the op's: csrc/bindings.cpp decodes the list in this order (``conv_geom``) and
+    exports the names (``hcb.conv_geom_fields``), which tests/test_conv_geom_cpu.py holds equal."""
+
+    N: int
+    H: int
+    W: int
+    C: int
+    ldx: int
+    P: int
+    Q: int
+    R: int
+    S: int
+    sh: int
+    sw: int
+    ph: int
+    pw: int
+    dh: int
+    dw: int
+    idh: int      # lhs (input) dilation: the zero-dilated dz of a strided data gradient
+    idw: int
+    Nout: int
+    K: int
+    Kpad: int
+    ldy: int
+    remap: int    # 1: GEMM pixel (p, q) -> output pixel (p*osh + oh0, q*osw + ow0) of [OH, OW]; 2: and zero the cell
+    OH: int
+    OW: int
+    osh: int
+    osw: int
+    beta: int
+    out_f32: int
+    relu: int = 0
+    stats_R: int = 0
+    splits: int = 1
+    oh0: int = 0
+    ow0: int = 0
+
+
+class WgradGeom(NamedTuple):
+    """A weight-gradient GEMM as conv_wgrad / conv_wgrad_p3 receive it (``geom``, 17 ints)."""
+
+    N: int
+    H: int
+    W: int
+    C: int
+    ldx: int
+    P: int
+    Q: int
+    R: int
+    S: int
+    sh: int
+    sw: int
+    ph: int
+    pw: int
+    dh: int
+    dw: int
+    Nout: int
+    ldy: int
+
+
+def fwd_geom(spec: ConvSpec, N: int, H: int, W: int, ldx: int, ldy: int, beta=0, out_f32=0, relu=0,
+             stats_R: int = 0) -> ConvGeom:
+    """The forward (and inference) GEMM of a conv over an [N, H, W] input with pixel stride ldx."""
+    P, Q = spec.out_hw(H, W)
+    K = spec.K
+    return ConvGeom(N, H, W, spec.cin_pad, ldx, P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
+                    spec.dh, spec.dw, 1, 1, spec.cout, K, _round_up(K, 64), ldy, 0, P, Q, 1, 1,
+                    1 if beta else 0, 1 if out_f32 else 0, 1 if relu else 0, int(stats_R))
+
+
+def dgrad_geom(spec: ConvSpec, N: int, H: int, W: int, P: int, Q: int, ldz: int, ldx: int, accumulate=False,
+               out_f32=0):
+    """(geometry, (M, K, taps)) of the one-GEMM data gradient dx[N,H,W] of dz[N,P,Q] (pixel stride
+    ldz; its channels read padded to 8). A strided 1x1 is a dense GEMM over the dz pixels whose rows
+    scatter to (p*sh, q*sw) -- remap 1, or 2 (the rows also zero the rest of their stride cell) when
+    the cells cover dx and nothing accumulates; everything else is a stride-1 correlation of the
+    lhs-dilated dz with the flipped kernel."""
+    Cdz = _round_up(spec.cout, 8)
+    K = spec.kh * spec.kw * Cdz
+    beta, out_f32 = 1 if accumulate else 0, 1 if out_f32 else 0
+    if (spec.sh > 1 or spec.sw > 1) and spec.kh == 1 and spec.kw == 1 and spec.pt == 0 and spec.pl == 0:
+        fill = REMAP_FILL and not accumulate and P * spec.sh >= H and Q * spec.sw >= W
+        g = ConvGeom(N, P, Q, Cdz, ldz, P, Q, 1, 1, 1, 1, 0, 0, 1, 1, 1, 1, spec.cin_pad, K, spec.Kpad_t, ldx,
+                     2 if fill else 1, H, W, spec.sh, spec.sw, beta, out_f32)
+        return g, (N * P * Q, K, 1)
+    g = ConvGeom(N, P, Q, Cdz, ldz, H, W, spec.kh, spec.kw, 1, 1, spec.dh * (spec.kh - 1) - spec.pt,
+                 spec.dw * (spec.kw - 1) - spec.pl, spec.dh, spec.dw, spec.sh, spec.sw, spec.cin_pad, K,
+                 spec.Kpad_t, ldx, 0, H, W, 1, 1, beta, out_f32)
+    return g, (N * H * W, K, spec.kh * spec.kw)
+
+
+def dgrad_phase_geom(spec: ConvSpec, N: int, H: int, W: int, P: int, Q: int, ldz: int, ldx: int, phase,
+                     accumulate=False, out_f32=0):
+    """(geometry, (M, K, taps)) of one stride phase (an entry of dgrad_phases) of a strided k x k data
+    gradient: a stride-1 GEMM over dz with the phase's sub-kernel, rows scattered to the phase's pixels."""
+    ph, pw, Hph, Wph, rs, ss, pad_t, pad_l = phase
+    Cdz = _round_up(spec.cout, 8)
+    taps = len(rs) * len(ss)
+    K = taps * Cdz
+    g = ConvGeom(N, P, Q, Cdz, ldz, Hph, Wph, len(rs), len(ss), 1, 1, pad_t, pad_l, 1, 1, 1, 1, spec.cin_pad, K,
+                 _round_up(K, 64), ldx, 1, H, W, spec.sh, spec.sw, 1 if accumulate else 0, 1 if out_f32 else 0,
+                 oh0=ph, ow0=pw)
+    return g, (N * Hph * Wph, K, taps)
+
+
+def wgrad_geom(spec: ConvSpec, N: int, H: int, W: int, P: int, Q: int, ldx: int, ldz: int) -> WgradGeom:
+    return WgradGeom(N, H, W, spec.cin_pad, ldx, P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
+                     spec.dh, spec.dw, spec.cout, ldz)
+
+
+# strided 1x1 data gradients zero their stride cells' gaps in the GEMM epilogue (False: a separate
+# zero-fill of dx first; the A/B switch HCB_REMAP_FILL=0)
+REMAP_FILL = os.environ.get("HCB_REMAP_FILL", "1") != "0"
+
+
 # ----------------------------------------------------------------- tile selection
 # cfg -> block tile; 0-3 register-staged main loop, 4-7 LDS-DMA ring (same tiles)
 _CONV_TILES = {0: (128, 128), 1: (128, 64), 2: (64, 64), 3: (64, 128),
@@ -437,11 +556,7 @@ def wgrad_cfg(Nout: int, K: int, M: int, taps: int = 1):
 
 def dgrad_problem(spec, N, H, W, P, Q):
     """(M, K) of the data-gradient GEMM of a conv."""
-    Cdz = spec.cout if spec.cout % 8 == 0 else _round_up(spec.cout, 8)
-    K = spec.kh * spec.kw * Cdz
-    if (spec.sh > 1 or spec.sw > 1) and spec.kh == 1 and spec.kw == 1 and spec.pt == 0 and spec.pl == 0:
-        return N * P * Q, K
-    return N * H * W, K
+    return dgrad_geom(spec, N, H, W, P, Q, 0, 0)[1][:2]
 
 
 def set_tuned(table: dict) -> None:
@@ -571,19 +686,55 @@ def wgrad_p3_plan(Nout: int, K: int, M: int, taps: int = 1):
     return c, splits
 
 
-def _plan3(cfg, M, N, K, device, taps: int = 1):
+def _plan(cfg, M, N, K, device, taps: int = 1, planner=conv_plan, clamp_k: bool = False, ws_cfgs=()):
+    """Normalise a cfg argument (None = tuned / heuristic, int, or (cfg, splits)). ``clamp_k``: at most
+    K // 64 splits; ``ws_cfgs``: the cfgs that need the split-K workspace with one split (stream-K)."""
     if cfg is None:
-        cfg, splits = p3_plan(M, N, K, taps)
+        cfg, splits = planner(M, N, K, taps)
     elif isinstance(cfg, (tuple, list)):
         cfg, splits = cfg
     else:
         splits = 1
-    splits = max(1, min(int(splits), max(K // 64, 1)))
+    if clamp_k:
+        splits = max(1, min(int(splits), max(K // 64, 1)))
     if _DET[0]:
         splits = 1
-    if splits != 1 or int(cfg) in _P3_STREAMK:
+    if splits > 1 or int(cfg) in ws_cfgs:
         ensure_splitk_workspace(device)
     return int(cfg), int(splits)
+
+
+# what the plane (fp32) GEMMs' plan adds to the 16-bit one
+_P3_PLAN = dict(planner=p3_plan, clamp_k=True, ws_cfgs=_P3_STREAMK)
+
+
+_SPLITS = ConvGeom._fields.index("splits")
+
+
+def _launch(x, w, y, geom: ConvGeom, cfg: int, splits: int, yres=None, bias=None, stats=None, stats_shift=None,
+            bnb=None, inf=None, w_lo=None):
+    """One forward / data-gradient / inference GEMM launch; the only place that tells the 16-bit ops
+    from the plane (fp32, bf16x6, conv_p3.hip) ones: by whether x is Planes. Epilogue: bias / stats /
+    stats_shift, or ``bnb`` (a BNBwdFuse: the consuming BN layer's backward reduction, z in the output's
+    type and the ReLU mask from y), or ``inf`` (gamma, beta, moving mean, moving variance, eps)."""
+    ops, g = _ext.ops(), list(geom)
+    g[_SPLITS] = splits  # the plan's split-K factor
+    p3 = is_planes(x)
+    pre = (x, w)
+    if p3:
+        w_lo = lo_pack(w) if w_lo is None else w_lo
+        assert w_lo is not None, "fp32 GEMMs need the mid / lo weight packs"
+        pre = (x.t, w, w_lo)
+    if bnb is not None:
+        op = ops.conv_p3_bnb if p3 else ops.conv_igemm_bnb
+        op(*pre, y, yres, g, cfg, bnb.z, _pl(bnb.y) if bnb.mode == 1 else None, ld(bnb.z), bnb.saved.mean,
+           bnb.saved.invstd, bnb.gamma, bnb.beta, bnb.acc, bnb.R, bnb.mode)
+    elif inf is not None:
+        op = ops.conv_p3_inf if p3 else ops.conv_igemm_inf
+        op(*pre, _pl(y), _pl(yres), g, cfg, *inf)
+    else:
+        op = ops.conv_p3 if p3 else ops.conv_igemm
+        op(*pre, y, yres, bias, stats, g, cfg, stats_shift)
 
 
 # ---------------------------------------------------------------- conv forward
@@ -592,22 +743,22 @@ def conv_forward(x, spec: ConvSpec, wpack, w_master, out, stats=None, bias=None,
     """out[N,P,Q,cout] = conv(x, W) (+bias) [ReLU]. GPU: fp32 acc, bf16 (or fp32) out + fused BN
     statistics: per-tile slab (stats_R=0) or fp32 atomics into stats_R replicas of [2][cout].
     ``stats_shift`` (fp32 [cout]): the statistics are sums of (v - shift) and (v - shift)^2, which
-    keeps the single-pass variance exact when |mean| >> std; the BN apply gets the same shift."""
-    if is_planes(x) or (native(x) and x.dtype == torch.float32):
-        return _conv_forward_p3(x, spec, wpack, out, stats, bias, cfg, relu, stats_R, residual, stats_shift)
+    keeps the single-pass variance exact when |mean| >> std; the BN apply gets the same shift.
+    fp32 (x Planes; an fp32 tensor is split first): the bf16x6 plane GEMM, fp32 out."""
     N, H, W, _ = x.shape
-    P, Q = spec.out_hw(H, W)
-    if native(x):
-        M = N * P * Q
-        cfg, splits = _plan(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw)
-        out_f32 = out.dtype == torch.float32
-        geom = [N, H, W, spec.cin_pad, ld(x), P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
-                spec.dh, spec.dw, 1, 1, spec.cout, spec.K, spec.Kpad, ld(out), 0, P, Q, 1, 1,
-                1 if residual is not None else 0, 1 if out_f32 else 0, 1 if relu else 0, int(stats_R), splits]
+    p3 = is_planes(x) or (native(x) and x.dtype == torch.float32)
+    if p3 or native(x):
+        if p3:
+            x = to_planes(x)
+            assert out.dtype == torch.float32, "fp32 conv needs an fp32 output"
+        geom = fwd_geom(spec, N, H, W, ld(x), ld(out), residual is not None, _f32o(out), relu, stats_R)
+        cfg, splits = _plan(cfg, N * geom.P * geom.Q, spec.cout, spec.K, x.device, spec.kh * spec.kw,
+                            **(_P3_PLAN if p3 else {}))
         if residual is not None:  # beta-accumulate epilogue: out = conv(x) + residual (same layout)
-            assert ld(residual) == ld(out) and residual.shape == out.shape
-        _ext.ops().conv_igemm(x, wpack, out, residual, bias, stats, geom, cfg, stats_shift, None)
+            assert ld(residual) == ld(out) and residual.shape == out.shape and (not p3 or residual.dtype == out.dtype)
+        _launch(x, wpack, out, geom, cfg, splits, yres=residual, bias=bias, stats=stats, stats_shift=stats_shift)
         return out
+    P, Q = spec.out_hw(H, W)
     xt = x.permute(0, 3, 1, 2)
     if spec.pt or spec.pb or spec.pl or spec.pr:
         xt = F.pad(xt, (spec.pl, spec.pr, spec.pt, spec.pb))
@@ -620,40 +771,6 @@ def conv_forward(x, spec: ConvSpec, wpack, w_master, out, stats=None, bias=None,
         y = y + residual
     out.copy_(y)
     return out
-
-
-def _conv_forward_p3(x, spec: ConvSpec, wpack, out, stats, bias, cfg, relu, stats_R, residual, stats_shift):
-    """fp32 forward conv on bf16 planes (bf16x6 MFMA GEMM, conv_p3.hip): x Planes (an fp32 tensor
-    is split first), fp32 out with the fused BN statistics / bias / ReLU / residual epilogue."""
-    x = to_planes(x)
-    N, H, W, _ = x.shape
-    P, Q = spec.out_hw(H, W)
-    M = N * P * Q
-    cfg, splits = _plan3(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw)
-    w_lo = lo_pack(wpack)
-    assert w_lo is not None and out.dtype == torch.float32, "fp32 conv needs the mid / lo weight packs and an fp32 output"
-    if residual is not None:
-        assert ld(residual) == ld(out) and residual.shape == out.shape and residual.dtype == torch.float32
-    geom = [N, H, W, spec.cin_pad, ld(x), P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
-            spec.dh, spec.dw, 1, 1, spec.cout, spec.K, spec.Kpad, ld(out), 0, P, Q, 1, 1,
-            1 if residual is not None else 0, 1, 1 if relu else 0, int(stats_R), splits]
-    _ext.ops().conv_p3(x.t, wpack, w_lo, out, residual, bias, stats, geom, cfg, stats_shift)
-    return out
-
-
-def _plan(cfg, M, N, K, device, taps: int = 1):
-    """Normalise a cfg argument (None = tuned / heuristic, int, or (cfg, splits))."""
-    if cfg is None:
-        cfg, splits = conv_plan(M, N, K, taps)
-    elif isinstance(cfg, (tuple, list)):
-        cfg, splits = cfg
-    else:
-        splits = 1
-    if _DET[0]:
-        splits = 1
-    if splits > 1:
-        ensure_splitk_workspace(device)
-    return int(cfg), int(splits)
 
 
 def zero_bufs(ts):
@@ -704,10 +821,6 @@ class BNBwdFuse:
             g.mul_(((xhat * self.gamma + self.beta) > 0).to(g.dtype))
         return g
 
-
-# strided 1x1 data gradients zero their stride cells' gaps in the GEMM epilogue (False: a separate
-# zero-fill of dx first; the A/B switch HCB_REMAP_FILL=0)
-REMAP_FILL = os.environ.get("HCB_REMAP_FILL", "1") != "0"
 
 # strided k x k data gradients as sh*sw stride-phase GEMMs (module switch, False: one GEMM over the
 # zero-dilated dz, which spends (sh*sw - 1)/(sh*sw) of its MFMA work on the inserted zeros)
@@ -761,53 +874,32 @@ def _phase_pack(wtr, spec: ConvSpec, Cdz: int, rs, ss):
 
 def dgrad_phase_problem(spec: ConvSpec, N: int, phase):
     """(M, K, taps) of one stride-phase data-grad GEMM (its tuning key)."""
-    _, _, Hph, Wph, rs, ss, _, _ = phase
-    Cdz = spec.cout if spec.cout % 8 == 0 else _round_up(spec.cout, 8)
-    return N * Hph * Wph, len(rs) * len(ss) * Cdz, len(rs) * len(ss)
+    return dgrad_phase_geom(spec, N, 0, 0, 0, 0, 0, 0, phase)[1]
+
+
+def _dgrad_plan(cfg, bnb, p3: bool, M, N, K, device, taps):
+    if cfg is None and bnb is not None and not p3:  # the 16-bit fused epilogue has its own tuning entry
+        cfg = _tuned.get(dgb_key(M, N, K, taps))
+    return _plan(cfg, M, N, K, device, taps, **(_P3_PLAN if p3 else {}))
 
 
 def dgrad_phase(dz, spec: ConvSpec, wtr, dx, accumulate: bool, phase, cfg=None, bnb: "BNBwdFuse" = None):
     """One stride-phase GEMM of a strided k x k data gradient (see dgrad_phases)."""
     N, P, Q, _ = dz.shape
     _, H, W, _ = dx.shape
-    ph, pw, Hph, Wph, rs, ss, pad_t, pad_l = phase
-    Cdz = spec.cout if spec.cout % 8 == 0 else _round_up(spec.cout, 8)
-    sub, Kph = _phase_pack(wtr, spec, Cdz, rs, ss)
-    M, _, taps = dgrad_phase_problem(spec, N, phase)
-    if dz.dtype == torch.float32:  # fp32 path: Planes operands
+    p3 = dz.dtype == torch.float32  # fp32 path: Planes operands
+    if p3:
+        dz = to_planes(dz)
+    geom, (M, K, taps) = dgrad_phase_geom(spec, N, H, W, P, Q, ld(dz), ld(dx), phase, accumulate, _f32o(dx))
+    rs, ss = phase[4], phase[5]
+    sub, _ = _phase_pack(wtr, spec, geom.C, rs, ss)
+    w_lo = None
+    if p3:
         lo = lo_pack(wtr)
         assert lo is not None, "fp32 data gradient needs the mid / lo weight packs"
-        w_lo, _ = _phase_pack(lo, spec, Cdz, rs, ss)
-        dz = to_planes(dz)
-        cfg, splits = _plan3(cfg, M, spec.cin_pad, Kph, dz.device, taps)
-        geom = [N, P, Q, Cdz, ld(dz), Hph, Wph, len(rs), len(ss), 1, 1, pad_t, pad_l, 1, 1, 1, 1,
-                spec.cin_pad, Kph, sub.shape[1], ld(dx), 1, H, W, spec.sh, spec.sw, 1 if accumulate else 0, 1,
-                0, 0, splits, ph, pw]
-        _p3_dgrad_launch(dz, sub, w_lo, dx, accumulate, geom, cfg, bnb)
-        return
-    geom = [N, P, Q, Cdz, ld(dz), Hph, Wph, len(rs), len(ss), 1, 1, pad_t, pad_l, 1, 1, 1, 1,
-            spec.cin_pad, Kph, sub.shape[1], ld(dx), 1, H, W, spec.sh, spec.sw, 1 if accumulate else 0, _f32o(dx)]
-    if cfg is None and bnb is not None:
-        cfg = _tuned.get(dgb_key(M, spec.cin_pad, Kph, taps))
-    cfg, splits = _plan(cfg, M, spec.cin_pad, Kph, dz.device, taps)
-    geom = geom + [0, 0, splits, ph, pw]
-    if bnb is not None:
-        _ext.ops().conv_igemm_bnb(dz, sub, dx, dx if accumulate else None, geom, cfg, bnb.z,
-                                  bnb.y if bnb.mode == 1 else None, ld(bnb.z), bnb.saved.mean,
-                                  bnb.saved.invstd, bnb.gamma, bnb.beta, bnb.acc, bnb.R, bnb.mode)
-    else:
-        _ext.ops().conv_igemm(dz, sub, dx, dx if accumulate else None, None, None, geom, cfg, None, None)
-
-
-def _p3_dgrad_launch(dz: "Planes", w, w_lo, dx, accumulate: bool, geom, cfg: int, bnb: "BNBwdFuse" = None):
-    """One fp32 (Planes) data-gradient GEMM, with the consuming BN layer's backward reduction fused
-    into its epilogue when ``bnb`` is given (z fp32, the ReLU mask from the hi plane of y)."""
-    if bnb is None:
-        _ext.ops().conv_p3(dz.t, w, w_lo, dx, dx if accumulate else None, None, None, geom, cfg, None)
-        return
-    _ext.ops().conv_p3_bnb(dz.t, w, w_lo, dx, dx if accumulate else None, geom, cfg, bnb.z,
-                           _pl(bnb.y) if bnb.mode == 1 else None, ld(bnb.z), bnb.saved.mean, bnb.saved.invstd,
-                           bnb.gamma, bnb.beta, bnb.acc, bnb.R, bnb.mode)
+        w_lo, _ = _phase_pack(lo, spec, geom.C, rs, ss)
+    cfg, splits = _dgrad_plan(cfg, bnb, p3, M, spec.cin_pad, K, dz.device, taps)
+    _launch(dz, sub, dx, geom, cfg, splits, yres=dx if accumulate else None, bnb=bnb, w_lo=w_lo)
 
 
 def uses_dgrad_phases(spec: ConvSpec, H: int, W: int) -> bool:
@@ -823,50 +915,20 @@ def conv_dgrad(dz, spec: ConvSpec, wtr, w_master, dx, accumulate: bool, cfg=None
     N, P, Q, _ = dz.shape
     _, H, W, _ = dx.shape
     if native(dz):
-        Cdz = spec.cout if spec.cout % 8 == 0 else _round_up(spec.cout, 8)
-        K = spec.kh * spec.kw * Cdz
-        Kpad = spec.Kpad_t
-        assert K <= Kpad
-        strided = spec.sh > 1 or spec.sw > 1
         if cfg is None and uses_dgrad_phases(spec, H, W):
             # one stride-1 GEMM per output parity over dz, rows scattered to (sh*i + ph, sw*j + pw)
             for phase in dgrad_phases(spec, H, W):
                 dgrad_phase(dz, spec, wtr, dx, accumulate, phase, None, bnb)
             return dx
-        if strided and spec.kh == 1 and spec.kw == 1 and spec.pt == 0 and spec.pl == 0:
-            # 1x1 strided: dense GEMM over dz pixels, scatter rows to (p*sh, q*sw)
-            M = N * P * Q
-            fill = REMAP_FILL and not accumulate and P * spec.sh >= H and Q * spec.sw >= W
-            if not accumulate and not fill:
-                dx.zero_()  # cells that do not tile dx: pixels past the last cell stay 0
-            geom = [N, P, Q, Cdz, ld(dz), P, Q, 1, 1, 1, 1, 0, 0, 1, 1, 1, 1, spec.cin_pad, K, Kpad,
-                    ld(dx), 2 if fill else 1, H, W, spec.sh, spec.sw, 1 if accumulate else 0, _f32o(dx)]
-        else:
-            M = N * H * W
-            pt = spec.dh * (spec.kh - 1) - spec.pt
-            pl = spec.dw * (spec.kw - 1) - spec.pl
-            geom = [N, P, Q, Cdz, ld(dz), H, W, spec.kh, spec.kw, 1, 1, pt, pl, spec.dh, spec.dw,
-                    spec.sh, spec.sw, spec.cin_pad, K, Kpad, ld(dx), 0, H, W, 1, 1,
-                    1 if accumulate else 0, _f32o(dx)]
-        taps = spec.kh * spec.kw
-        if dz.dtype == torch.float32:  # fp32 path: Planes operands (bf16x6 GEMM, conv_p3.hip)
-            w_lo = lo_pack(wtr)
-            assert w_lo is not None, "fp32 data gradient needs the mid / lo weight packs"
+        p3 = dz.dtype == torch.float32  # fp32 path: Planes operands (bf16x6 GEMM, conv_p3.hip)
+        if p3:
             dz = to_planes(dz)
-            geom[4] = ld(dz)
-            cfg, splits = _plan3(cfg, M, spec.cin_pad, K, dz.device, taps)
-            _p3_dgrad_launch(dz, wtr, w_lo, dx, accumulate, geom + [0, 0, splits], cfg, bnb)
-            return dx
-        if cfg is None and bnb is not None:
-            cfg = _tuned.get(dgb_key(M, spec.cin_pad, K, taps))
-        cfg, splits = _plan(cfg, M, spec.cin_pad, K, dz.device, taps)
-        geom = geom + [0, 0, splits]
-        if bnb is not None:
-            _ext.ops().conv_igemm_bnb(dz, wtr, dx, dx if accumulate else None, geom, cfg, bnb.z,
-                                      bnb.y if bnb.mode == 1 else None, ld(bnb.z), bnb.saved.mean,
-                                      bnb.saved.invstd, bnb.gamma, bnb.beta, bnb.acc, bnb.R, bnb.mode)
-        else:
-            _ext.ops().conv_igemm(dz, wtr, dx, dx if accumulate else None, None, None, geom, cfg, None, None)
+        geom, (M, K, taps) = dgrad_geom(spec, N, H, W, P, Q, ld(dz), ld(dx), accumulate, _f32o(dx))
+        assert K <= geom.Kpad
+        if geom.remap == 1 and not accumulate:
+            dx.zero_()  # cells that do not tile dx: pixels past the last cell stay 0
+        cfg, splits = _dgrad_plan(cfg, bnb, p3, M, spec.cin_pad, K, dz.device, taps)
+        _launch(dz, wtr, dx, geom, cfg, splits, yres=dx if accumulate else None, bnb=bnb)
         return dx
     Hp = H + spec.pt + spec.pb
     Wp = W + spec.pl + spec.pr
@@ -888,24 +950,18 @@ def conv_wgrad(dz, x, spec: ConvSpec, dw, cfg=None):
     """dw[cout, kh, kw, cin_pad] (fp32) += sum over pixels of dz (x) im2col(x)."""
     N, H, W, _ = x.shape
     _, P, Q, _ = dz.shape
-    if native(dz) and dz.dtype == torch.float32:  # fp32 path: Planes operands (conv_p3.hip)
-        dz, x = to_planes(dz), to_planes(x)
-        M = N * P * Q
-        cfg, splits = cfg if cfg is not None else wgrad_p3_plan(spec.cout, spec.K, M, spec.kh * spec.kw)
-        if _DET[0]:
-            splits = 1
-        geom = [N, H, W, spec.cin_pad, ld(x), P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
-                spec.dh, spec.dw, spec.cout, ld(dz)]
-        _ext.ops().conv_wgrad_p3(dz.t, x.t, dw, geom, int(cfg), int(splits))
-        return dw
     if native(dz):
-        M = N * P * Q
-        cfg, splits = cfg if cfg is not None else wgrad_cfg(spec.cout, spec.K, M, spec.kh * spec.kw)
+        p3 = dz.dtype == torch.float32  # fp32 path: Planes operands (conv_p3.hip)
+        if p3:
+            dz, x = to_planes(dz), to_planes(x)
+        geom = wgrad_geom(spec, N, H, W, P, Q, ld(x), ld(dz))
+        if cfg is None:
+            cfg = (wgrad_p3_plan if p3 else wgrad_cfg)(spec.cout, spec.K, N * P * Q, spec.kh * spec.kw)
+        cfg, splits = cfg
         if _DET[0]:
             splits = 1  # sole writer per dW tile: no float atomics
-        geom = [N, H, W, spec.cin_pad, ld(x), P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
-                spec.dh, spec.dw, spec.cout, ld(dz)]
-        _ext.ops().conv_wgrad(dz, x, dw, geom, cfg, splits)
+        op = _ext.ops().conv_wgrad_p3 if p3 else _ext.ops().conv_wgrad
+        op(_pl(dz), _pl(x), dw, list(geom), int(cfg), int(splits))
         return dw
     xt = x.permute(0, 3, 1, 2)
     if spec.pt or spec.pb or spec.pl or spec.pr:
@@ -947,28 +1003,18 @@ def conv_bn_inference(x, spec: ConvSpec, wpack, w_master, gamma, beta, running_m
         return bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu, residual=residual)
     if p3:
         x = to_planes(x)
+        assert out.dtype == torch.float32, "fp32 conv needs an fp32 (or Planes) output"
         if residual is not None:  # the epilogue reads a residual in out's format (fp32, or planes)
             residual = to_planes(residual) if is_planes(out) else from_planes(residual)
-        cfg, splits = _plan3(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw)
-        if cfg in _P3_PERSIST:
-            cfg = _P3_PERSIST[cfg]
-        w_lo = lo_pack(wpack)
-        assert w_lo is not None and out.dtype == torch.float32, "fp32 conv needs the mid / lo weight packs"
-    else:
-        cfg, splits = _plan(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw)
-        if cfg in PATCH_CFGS:  # no split-K on the twin, as launch_conv_igemm's own fallback
-            cfg, splits = _PATCH_TWIN[cfg], 1
+    cfg, splits = _plan(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw, **(_P3_PLAN if p3 else {}))
+    if p3:
+        cfg = _P3_PERSIST.get(cfg, cfg)
+    elif cfg in PATCH_CFGS:  # no split-K on the twin, as launch_conv_igemm's own fallback
+        cfg, splits = _PATCH_TWIN[cfg], 1
     if residual is not None:
         assert ld(residual) == ld(out) and residual.shape == out.shape and residual.dtype == out.dtype
-    geom = [N, H, W, spec.cin_pad, ld(x), P, Q, spec.kh, spec.kw, spec.sh, spec.sw, spec.pt, spec.pl,
-            spec.dh, spec.dw, 1, 1, spec.cout, spec.K, spec.Kpad, ld(out), 0, P, Q, 1, 1,
-            1 if residual is not None else 0, 0 if is_planes(out) else _f32o(out), 1 if relu else 0, 0, splits]
-    if p3:
-        _ext.ops().conv_p3_inf(x.t, wpack, w_lo, _pl(out), _pl(residual), geom, cfg, gamma, beta, running_mean,
-                               running_var, float(eps))
-    else:
-        _ext.ops().conv_igemm_inf(x, wpack, out, residual, geom, cfg, gamma, beta, running_mean, running_var,
-                                  float(eps))
+    geom = fwd_geom(spec, N, H, W, ld(x), ld(out), residual is not None, not is_planes(out) and _f32o(out), relu)
+    _launch(x, wpack, out, geom, cfg, splits, yres=residual, inf=(gamma, beta, running_mean, running_var, float(eps)))
     return out
 
 

@@ -98,44 +98,80 @@ static int64_t x_span_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t 
   return ldx >= C ? ((N * H * W - 1) * ldx + C) * e : N * H * W * ldx * e;
 }
 
-// geom = [N,H,W,C,ldx, P,Q,R,S, sh,sw,ph,pw,dh,dw,idh,idw, Nout,K,Kpad,ldy,
-//         remap,OH,OW,osh,osw, beta,out_f32]
+// The two geometry lists, decoded HERE and nowhere else: entry i of the list is field i of the table,
+// the order of ops/functional.py's ConvGeom / WgradGeom records (conv_geom_fields exports the names
+// and tests/test_conv_geom_cpu.py holds the two orders equal).
+template <class P>
+struct GeomField {
+  const char* name;
+  int P::*field;
+};
+using CP = hcb::ConvParams;
+using WP = hcb::WgradParams;
+const GeomField<CP> kConvGeom[] = {
+    {"N", &CP::N}, {"H", &CP::H}, {"W", &CP::W}, {"C", &CP::C}, {"ldx", &CP::ldx},
+    {"P", &CP::P}, {"Q", &CP::Q}, {"R", &CP::R}, {"S", &CP::S},
+    {"sh", &CP::stride_h}, {"sw", &CP::stride_w}, {"ph", &CP::pad_h}, {"pw", &CP::pad_w},
+    {"dh", &CP::dil_h}, {"dw", &CP::dil_w}, {"idh", &CP::idil_h}, {"idw", &CP::idil_w},
+    {"Nout", &CP::Nout}, {"K", &CP::K}, {"Kpad", &CP::Kpad}, {"ldy", &CP::ldy},
+    {"remap", &CP::remap}, {"OH", &CP::OH}, {"OW", &CP::OW}, {"osh", &CP::osh}, {"osw", &CP::osw},
+    {"beta", &CP::beta}, {"out_f32", &CP::out_f32},
+    {"relu", &CP::relu}, {"stats_R", &CP::stats_R}, {"splits", &CP::splits}, {"oh0", &CP::oh0}, {"ow0", &CP::ow0}};
+const GeomField<WP> kWgradGeom[] = {
+    {"N", &WP::N}, {"H", &WP::H}, {"W", &WP::W}, {"C", &WP::C}, {"ldx", &WP::ldx},
+    {"P", &WP::P}, {"Q", &WP::Q}, {"R", &WP::R}, {"S", &WP::S},
+    {"sh", &WP::stride_h}, {"sw", &WP::stride_w}, {"ph", &WP::pad_h}, {"pw", &WP::pad_w},
+    {"dh", &WP::dil_h}, {"dw", &WP::dil_w}, {"Nout", &WP::Nout}, {"ldy", &WP::ldy}};
+
+template <class P, size_t n>
+P decode_geom(const GeomField<P> (&fields)[n], at::IntArrayRef g, const char* op) {
+  TORCH_CHECK(g.size() == n, "hcb.", op, ": geom must have ", n, " entries");
+  P p{};
+  for (size_t i = 0; i < n; ++i) p.*fields[i].field = (int)g[i];
+  p.M = p.N * p.P * p.Q;
+  return p;
+}
+
+std::vector<std::string> conv_geom_fields(std::string kind) {
+  std::vector<std::string> out;
+  if (kind == "conv") {
+    for (const auto& f : kConvGeom) out.push_back(f.name);
+  } else if (kind == "wgrad") {
+    for (const auto& f : kWgradGeom) out.push_back(f.name);
+  } else {
+    TORCH_CHECK(false, "hcb.conv_geom_fields: kind is conv or wgrad");
+  }
+  return out;
+}
+
+// output rows of a GEMM (after remap) and the bytes that `rows` rows of Nout columns, read and written
+// as whole 8-column vectors, span at row stride ld
+int64_t out_rows(const hcb::ConvParams& p) { return p.remap ? (int64_t)p.N * p.OH * p.OW : (int64_t)p.M; }
+int64_t pad8(int64_t n) { return (n + 7) / 8 * 8; }
+int64_t out_span_bytes(int64_t rows, int64_t ld, int64_t Nout, int64_t esz) {
+  return ((rows - 1) * ld + pad8(Nout)) * esz;
+}
+
+// the geometry, operand and byte-range checks every forward / data-gradient / inference GEMM shares
+// (x: the 16-bit input, or plane 0 of a plane input); statistics and split-K are attached per family
 hcb::ConvParams conv_params(const Tensor& x, const Tensor& w, const Tensor& y, const c10::optional<Tensor>& yres,
-                            const c10::optional<Tensor>& bias, const c10::optional<Tensor>& stats,
-                            at::IntArrayRef g, int64_t cfg) {
-  TORCH_CHECK(g.size() >= 28 && g.size() <= 33,
-              "hcb.conv_igemm: geom must have 28 (+relu, +stats_R, +splits, +remap origin h, w) entries");
-  const bool f32 = check_act_or_f32(x, "x");  // fp32: bf16x6 path (w = high pack, w_lo set by the caller)
+                            const c10::optional<Tensor>& bias, at::IntArrayRef g) {
+  hcb::ConvParams p = decode_geom(kConvGeom, g, "conv_igemm");
+  check_act(x, "x");
   check_act(w, "w");
   check_cuda(y, "y");
-  hcb::ConvParams p{};
-  p.N = g[0]; p.H = g[1]; p.W = g[2]; p.C = g[3]; p.ldx = g[4];
-  p.P = g[5]; p.Q = g[6]; p.R = g[7]; p.S = g[8];
-  p.stride_h = g[9]; p.stride_w = g[10]; p.pad_h = g[11]; p.pad_w = g[12];
-  p.dil_h = g[13]; p.dil_w = g[14]; p.idil_h = g[15]; p.idil_w = g[16];
-  p.Nout = g[17]; p.K = g[18]; p.Kpad = g[19]; p.ldy = g[20];
-  p.remap = g[21]; p.OH = g[22]; p.OW = g[23]; p.osh = g[24]; p.osw = g[25];
-  p.beta = g[26]; p.out_f32 = g[27];
-  p.relu = g.size() > 28 ? (int)g[28] : 0;
-  p.stats_R = g.size() > 29 ? (int)g[29] : 0;
-  p.splits = g.size() > 30 ? (int)g[30] : 1;
-  p.oh0 = g.size() > 31 ? (int)g[31] : 0;
-  p.ow0 = g.size() > 32 ? (int)g[32] : 0;
-  p.M = p.N * p.P * p.Q;
   TORCH_CHECK(p.C % 8 == 0 && p.ldx % 8 == 0 && (p.ldx >= p.C || p.C % p.ldx == 0),
               "hcb.conv_igemm: C, ldx must be multiples of 8 (ldx < C: a row window, C a multiple of ldx)");
   TORCH_CHECK(p.Kpad % 64 == 0 && p.Kpad >= p.K && p.K == p.R * p.S * p.C,
               "hcb.conv_igemm: Kpad must be a multiple of 64 >= K = R*S*C");
-  TORCH_CHECK(p.ldy % 8 == 0 && p.ldy >= ((p.Nout + 7) / 8) * 8, "hcb.conv_igemm: bad ldy");
+  TORCH_CHECK(p.ldy % 8 == 0 && p.ldy >= pad8(p.Nout), "hcb.conv_igemm: bad ldy");
   TORCH_CHECK(p.idil_h >= 1 && p.idil_w >= 1 && p.dil_h >= 1 && p.dil_w >= 1, "hcb.conv_igemm: bad dilation");
   TORCH_CHECK(p.M > 0 && p.Nout > 0, "hcb.conv_igemm: empty problem");
-  const int64_t xe = f32 ? 4 : 2;
-  int64_t xb = x_span_bytes(p.N, p.H, p.W, p.C, p.ldx, xe);
+  int64_t xb = x_span_bytes(p.N, p.H, p.W, p.C, p.ldx, 2);
   int64_t wb = (int64_t)p.Nout * p.Kpad * 2;
   TORCH_CHECK(xb < (1ll << 31) && wb < (1ll << 31), "hcb.conv_igemm: operand exceeds 2 GiB buffer range");
   check_range(x, xb, "x");
   check_range(w, wb, "w");
-  int64_t rows = p.remap ? (int64_t)p.N * p.OH * p.OW : (int64_t)p.M;
   TORCH_CHECK(p.remap >= 0 && p.remap <= 2, "hcb.conv_igemm: remap is 0, 1 or 2");
   if (p.remap) {
     TORCH_CHECK(p.oh0 >= 0 && p.ow0 >= 0 && (p.P - 1) * p.osh + p.oh0 < p.OH && (p.Q - 1) * p.osw + p.ow0 < p.OW,
@@ -146,50 +182,61 @@ hcb::ConvParams conv_params(const Tensor& x, const Tensor& w, const Tensor& y, c
   } else {
     TORCH_CHECK(p.oh0 == 0 && p.ow0 == 0, "hcb.conv_igemm: a remap origin needs remap");
   }
-  int64_t esz = p.out_f32 ? 4 : 2;
-  TORCH_CHECK(!f32 || p.out_f32, "hcb.conv_igemm: fp32 inputs give an fp32 output (out_f32)");
+  const int64_t span = out_span_bytes(out_rows(p), p.ldy, p.Nout, p.out_f32 ? 4 : 2);
   TORCH_CHECK(y.scalar_type() == (p.out_f32 ? at::kFloat : kAct), "hcb.conv_igemm: y dtype");
-  check_range(y, rows * p.ldy * esz - (p.ldy - ((p.Nout + 7) / 8) * 8) * esz, "y");
+  check_range(y, span, "y");
   check_align16(x.data_ptr(), "x");
   check_align16(w.data_ptr(), "w");
   check_align16(y.data_ptr(), "y");
   p.x = x.data_ptr();
   p.w = w.data_ptr();
   p.y = y.data_ptr();
-  p.yres = nullptr;
   if (p.beta) {
     TORCH_CHECK(yres.has_value(), "hcb.conv_igemm: beta needs yres");
-    check_range(*yres, rows * p.ldy * esz - (p.ldy - ((p.Nout + 7) / 8) * 8) * esz, "yres");
+    check_range(*yres, span, "yres");
     check_align16(yres->data_ptr(), "yres");
     p.yres = yres->data_ptr();
   }
-  p.bias = nullptr;
   if (bias.has_value()) {
     check_f32(*bias, "bias");
     TORCH_CHECK(bias->numel() >= p.Nout, "hcb.conv_igemm: bias too small");
     p.bias = bias->data_ptr<float>();
   }
-  p.stats = nullptr;
-  if (stats.has_value()) {
-    check_f32(*stats, "stats");
-    int tiles_m = (p.M + hcb::conv_tile_m(cfg) - 1) / hcb::conv_tile_m(cfg);
-    int64_t rows = p.stats_R > 0 ? p.stats_R : tiles_m;
-    TORCH_CHECK(stats->numel() >= rows * 2 * p.Nout, "hcb.conv_igemm: stats buffer too small");
-    p.stats = stats->data_ptr<float>();
-  }
   p.x_bytes = (uint32_t)xb;
   p.w_bytes = (uint32_t)wb;
-  TORCH_CHECK(p.splits >= 1 && p.splits <= p.Kpad / 64, "hcb.conv_igemm: 1 <= splits <= k-steps");
-  if (p.splits > 1) {
-    TORCH_CHECK(hcb::conv_cfg_splitk((int)cfg), "hcb.conv_igemm: split-K needs an LDS-DMA config (cfg >= 4)");
-    TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.conv_igemm: split-K workspace not set");
-    const int bm = hcb::conv_tile_m((int)cfg), bn = hcb::conv_tile_n((int)cfg);
-    const int64_t tiles = (int64_t)((p.M + bm - 1) / bm) * ((p.Nout + bn - 1) / bn);
-    TORCH_CHECK(tiles * p.splits * bm * bn * 4 <= g_splitk_ws_bytes, "hcb.conv_igemm: split-K workspace too small");
-    TORCH_CHECK(tiles <= g_splitk_cnt_n, "hcb.conv_igemm: split-K counter array too small");
-    p.ws = g_splitk_ws;
-    p.cnt = g_splitk_cnt;
-  }
+  return p;
+}
+
+// the statistics buffer of a GEMM epilogue: stats_R replicas, or one slab per row tile of tile_m rows
+void attach_stats(hcb::ConvParams& p, const c10::optional<Tensor>& stats, int tile_m, const char* op) {
+  if (!stats.has_value()) return;
+  check_f32(*stats, "stats");
+  const int64_t rows = p.stats_R > 0 ? p.stats_R : (p.M + tile_m - 1) / tile_m;
+  TORCH_CHECK(stats->numel() >= rows * 2 * p.Nout, "hcb.", op, ": stats buffer too small");
+  p.stats = stats->data_ptr<float>();
+}
+
+// the split-K workspace of a GEMM of bm x bn tiles with p.splits > 1
+void attach_splitk(hcb::ConvParams& p, int bm, int bn, const char* op) {
+  TORCH_CHECK(p.splits >= 1 && p.splits <= p.Kpad / 64, "hcb.", op, ": 1 <= splits <= k-steps");
+  if (p.splits == 1) return;
+  const int64_t tiles = (int64_t)((p.M + bm - 1) / bm) * ((p.Nout + bn - 1) / bn);
+  TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.", op, ": split-K workspace not set");
+  TORCH_CHECK(tiles * p.splits * bm * bn * 4 <= g_splitk_ws_bytes, "hcb.", op, ": split-K workspace too small");
+  TORCH_CHECK(tiles <= g_splitk_cnt_n, "hcb.", op, ": split-K counter array too small");
+  p.ws = g_splitk_ws;
+  p.cnt = g_splitk_cnt;
+}
+
+// a 16-bit GEMM (conv_igemm.hip): conv_params plus the statistics slab and split-K against the conv tiles
+hcb::ConvParams igemm_params(const Tensor& x, const Tensor& w, const Tensor& y, const c10::optional<Tensor>& yres,
+                             const c10::optional<Tensor>& bias, const c10::optional<Tensor>& stats,
+                             at::IntArrayRef g, int64_t cfg) {
+  hcb::ConvParams p = conv_params(x, w, y, yres, bias, g);
+  attach_stats(p, stats, hcb::conv_tile_m((int)cfg), "conv_igemm");
+  TORCH_CHECK(p.splits <= 1 || hcb::conv_cfg_splitk((int)cfg),
+              "hcb.conv_igemm: split-K needs an LDS-DMA config (cfg >= 4)");
+  attach_splitk(p, hcb::conv_tile_m((int)cfg), hcb::conv_tile_n((int)cfg), "conv_igemm");
   return p;
 }
 
@@ -219,14 +266,10 @@ const float* opt_f32(const c10::optional<Tensor>& t, int64_t n, const char* what
 
 void conv_igemm(const Tensor& x, const Tensor& w, const Tensor& y, const c10::optional<Tensor>& yres,
                 const c10::optional<Tensor>& bias, const c10::optional<Tensor>& stats,
-                at::IntArrayRef g, int64_t cfg, const c10::optional<Tensor>& stats_shift,
-                const c10::optional<Tensor>& w_lo) {
-  hcb::ConvParams p = conv_params(x, w, y, yres, bias, stats, g, cfg);
+                at::IntArrayRef g, int64_t cfg, const c10::optional<Tensor>& stats_shift) {
+  hcb::ConvParams p = igemm_params(x, w, y, yres, bias, stats, g, cfg);
   TORCH_CHECK(!stats_shift.has_value() || p.stats != nullptr, "hcb.conv_igemm: stats_shift without stats");
   p.stats_shift = opt_f32(stats_shift, p.Nout, "stats_shift");
-  p.w_lo = p.w_lo2 = nullptr;
-  TORCH_CHECK(x.scalar_type() != at::kFloat && !w_lo.has_value(),
-              "hcb.conv_igemm: 16-bit operands only (fp32 runs on the plane GEMMs: hcb.conv_p3)");
   hcb::launch_conv_igemm(p, (int)cfg, cur_stream());
 }
 
@@ -241,14 +284,12 @@ void set_bnb(hcb::ConvParams& p, const Tensor& z, const c10::optional<Tensor>& y
   TORCH_CHECK(!p.relu && p.bias == nullptr, "hcb.conv_igemm_bnb: no bias / relu");
   TORCH_CHECK(p.out_f32 == (f32 ? 1 : 0), "hcb.conv_igemm_bnb: 16-bit output (fp32 on the fp32 path)");
   TORCH_CHECK(mode >= 0 && mode <= 2 && R >= 1, "hcb.conv_igemm_bnb: bad mode / R");
-  TORCH_CHECK(ld % 8 == 0 && ld >= ((p.Nout + 7) / 8) * 8, "hcb.conv_igemm_bnb: bad ld");
-  int64_t rows = p.remap ? (int64_t)p.N * p.OH * p.OW : (int64_t)p.M;
-  const int64_t zsz = f32 ? 4 : 2;
+  TORCH_CHECK(ld % 8 == 0 && ld >= pad8(p.Nout), "hcb.conv_igemm_bnb: bad ld");
   if (f32)
     check_f32(z, "z");
   else
     check_act(z, "z");
-  check_range(z, ((rows - 1) * ld + ((p.Nout + 7) / 8) * 8) * zsz, "z");
+  check_range(z, out_span_bytes(out_rows(p), ld, p.Nout, f32 ? 4 : 2), "z");
   check_align16(z.data_ptr(), "z");
   p.bnb_y = nullptr;
   if (mode == 1) {
@@ -257,7 +298,7 @@ void set_bnb(hcb::ConvParams& p, const Tensor& z, const c10::optional<Tensor>& y
       check_planes(*yact, "y");
     else
       check_act(*yact, "y");
-    check_range(*yact, ((rows - 1) * ld + ((p.Nout + 7) / 8) * 8) * 2, "y");
+    check_range(*yact, out_span_bytes(out_rows(p), ld, p.Nout, 2), "y");
     check_align16(yact->data_ptr(), "y");
     p.bnb_y = yact->data_ptr();
   }
@@ -286,7 +327,7 @@ void conv_igemm_bnb(const Tensor& x, const Tensor& w, const Tensor& y, const c10
                     at::IntArrayRef g, int64_t cfg, const Tensor& z, const c10::optional<Tensor>& yact,
                     int64_t ld, const Tensor& mean, const Tensor& invstd, const Tensor& gamma, const Tensor& beta,
                     const Tensor& acc, int64_t R, int64_t mode) {
-  hcb::ConvParams p = conv_params(x, w, y, yres, c10::nullopt, c10::nullopt, g, cfg);
+  hcb::ConvParams p = igemm_params(x, w, y, yres, c10::nullopt, c10::nullopt, g, cfg);
   set_bnb(p, z, yact, ld, mean, invstd, gamma, beta, acc, R, mode, false);
   hcb::launch_conv_igemm(p, (int)cfg, cur_stream());
 }
@@ -317,18 +358,12 @@ void conv_igemm_inf(const Tensor& x, const Tensor& w, const Tensor& y, const c10
                     at::IntArrayRef g, int64_t cfg, const Tensor& gamma, const Tensor& beta, const Tensor& mean,
                     const Tensor& var, double eps) {
   TORCH_CHECK(hcb::conv_cfg_has_inf((int)cfg), "hcb.conv_igemm_inf: cfg 0..16 (a patch cfg runs its LDS-DMA twin)");
-  hcb::ConvParams p = conv_params(x, w, y, res, c10::nullopt, c10::nullopt, g, cfg);
+  hcb::ConvParams p = igemm_params(x, w, y, res, c10::nullopt, c10::nullopt, g, cfg);
   TORCH_CHECK(x.scalar_type() != at::kFloat && !p.out_f32,
               "hcb.conv_igemm_inf: 16-bit operands and output (fp32 runs on the plane GEMMs: hcb.conv_p3_inf)");
   TORCH_CHECK(!p.beta || res->scalar_type() == y.scalar_type(), "hcb.conv_igemm_inf: res dtype differs from y");
-  p.w_lo = p.w_lo2 = nullptr;
   set_inf(p, y, gamma, beta, mean, var, eps);
   hcb::launch_conv_igemm(p, (int)cfg, cur_stream());
-}
-
-int64_t conv_tiles_m(int64_t M, int64_t cfg) {
-  int t = hcb::conv_tile_m((int)cfg);
-  return (M + t - 1) / t;
 }
 
 // the rows of a family's table (gemm_cfg.h), flat, 12 per cfg: cfg, kind, WM, WN, TM, TN, slot depth,
@@ -356,37 +391,24 @@ std::vector<int64_t> gemm_cfg_table(std::string family) {
   return out;
 }
 
-// geom = [N,H,W,C,ldx, P,Q,R,S, sh,sw,ph,pw,dh,dw, Nout,ldy]
-void conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArrayRef g, int64_t cfg,
-                int64_t splits) {
-  TORCH_CHECK(g.size() == 17, "hcb.conv_wgrad: geom must have 17 entries");
-  const bool f32 = same_act(dy, x, "x");
-  TORCH_CHECK(!f32, "hcb.conv_wgrad: 16-bit operands only (fp32 runs on the plane GEMMs: hcb.conv_wgrad_p3)");
+// The weight-gradient GEMM of both precisions: the 17-entry geometry, its checks, the k-step split and
+// the fast divisors. dy / x: the 16-bit operands, or plane 0 of plane operands; op: "conv_wgrad" /
+// "conv_wgrad_p3". Returns the split count that leaves no empty split.
+int wgrad_params(hcb::WgradParams& p, const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArrayRef g,
+                 int64_t splits, const char* op) {
+  p = decode_geom(kWgradGeom, g, op);
   check_f32(dw, "dw");
-  hcb::WgradParams p{};
-  const int64_t e = 2;
-  p.N = g[0]; p.H = g[1]; p.W = g[2]; p.C = g[3]; p.ldx = g[4];
-  p.P = g[5]; p.Q = g[6]; p.R = g[7]; p.S = g[8];
-  p.stride_h = g[9]; p.stride_w = g[10]; p.pad_h = g[11]; p.pad_w = g[12];
-  p.dil_h = g[13]; p.dil_w = g[14];
-  p.Nout = g[15]; p.ldy = g[16];
   p.K = p.R * p.S * p.C;
-  p.M = p.N * p.P * p.Q;
-  TORCH_CHECK(p.C % 8 == 0 && p.ldx % 8 == 0, "hcb.conv_wgrad: C, ldx multiples of 8");
-  TORCH_CHECK(p.ldy % 8 == 0 && p.ldy >= p.Nout, "hcb.conv_wgrad: bad ldy");
-  TORCH_CHECK(splits >= 1, "hcb.conv_wgrad: splits >= 1");
-  int64_t xb = x_span_bytes(p.N, p.H, p.W, p.C, p.ldx, e);
-  int64_t yb = ((int64_t)p.M - 1) * p.ldy * e + (int64_t)((p.Nout + 7) / 8) * 8 * e;
-  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31), "hcb.conv_wgrad: operand exceeds 2 GiB");
-  check_range(x, xb, "x");
-  check_range(dy, yb, "dy");
+  TORCH_CHECK(p.C % 8 == 0 && p.ldx % 8 == 0, "hcb.", op, ": C, ldx multiples of 8");
+  TORCH_CHECK(p.ldy % 8 == 0 && p.ldy >= p.Nout, "hcb.", op, ": bad ldy");
+  TORCH_CHECK(splits >= 1, "hcb.", op, ": splits >= 1");
+  const int64_t xb = x_span_bytes(p.N, p.H, p.W, p.C, p.ldx, 2);
+  const int64_t yb = out_span_bytes(p.M, p.ldy, p.Nout, 2);
+  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31), "hcb.", op, ": operand exceeds 2 GiB");
   check_range(dw, (int64_t)p.Nout * p.K * 4, "dw");
-  check_align16(x.data_ptr(), "x");
-  check_align16(dy.data_ptr(), "dy");
-  int nkt = (p.M + 63) / 64;
-  int per = (nkt + (int)splits - 1) / (int)splits;
+  const int nkt = (p.M + 63) / 64;
+  const int per = (nkt + (int)splits - 1) / (int)splits;
   p.ksteps_per_split = per;
-  int eff_splits = (nkt + per - 1) / per;
   p.fd_pq = hcb::make_fastdiv((uint32_t)(p.P * p.Q));
   p.fd_q = hcb::make_fastdiv((uint32_t)p.Q);
   p.fd_c = hcb::make_fastdiv((uint32_t)p.C);
@@ -396,6 +418,19 @@ void conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArra
   p.dw = dw.data_ptr<float>();
   p.dy_bytes = (uint32_t)yb;
   p.x_bytes = (uint32_t)xb;
+  return (nkt + per - 1) / per;
+}
+
+void conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArrayRef g, int64_t cfg,
+                int64_t splits) {
+  const bool f32 = same_act(dy, x, "x");
+  TORCH_CHECK(!f32, "hcb.conv_wgrad: 16-bit operands only (fp32 runs on the plane GEMMs: hcb.conv_wgrad_p3)");
+  hcb::WgradParams p;
+  const int eff_splits = wgrad_params(p, dy, x, dw, g, splits, "conv_wgrad");
+  check_range(x, p.x_bytes, "x");
+  check_range(dy, p.dy_bytes, "dy");
+  check_align16(x.data_ptr(), "x");
+  check_align16(dy.data_ptr(), "dy");
   hcb::launch_conv_wgrad(p, (int)cfg, eff_splits, cur_stream());
 }
 
@@ -740,13 +775,6 @@ void weight_pack(const Tensor& master, const Tensor& pack, const Tensor& table, 
                           (int)table.size(0), max_work, cur_stream(), (int)lo, pstride);
 }
 
-void cast_f32_bf16(const Tensor& x, const Tensor& y) {
-  check_f32(x, "x");
-  check_act(y, "y");
-  TORCH_CHECK(x.numel() == y.numel() && x.is_contiguous() && y.is_contiguous(), "hcb.cast: shape");
-  hcb::launch_cast_f32_bf16(x.data_ptr<float>(), (uint16_t*)y.data_ptr(), x.numel(), cur_stream());
-}
-
 void add_bf16(const Tensor& a, const Tensor& b, const Tensor& y) {
   check_act(a, "a");
   check_act(b, "b");
@@ -978,18 +1006,6 @@ void dropout_bwd(const Tensor& dy, const Tensor& mask, const Tensor& dx, double 
                           f32);
 }
 
-void scale_f32(const Tensor& x, double s) {
-  check_f32(x, "x");
-  TORCH_CHECK(x.is_contiguous(), "hcb.scale_f32: contiguous");
-  hcb::launch_scale_f32(x.data_ptr<float>(), x.numel(), (float)s, cur_stream());
-}
-
-void l2norm_sq(const Tensor& x, const Tensor& out) {
-  check_f32(x, "x");
-  check_f32(out, "out");
-  hcb::launch_l2norm_sq(x.data_ptr<float>(), x.numel(), out.data_ptr<float>(), cur_stream());
-}
-
 void synth_images(const Tensor& out, int64_t C, int64_t Cpad, double mean, double std, int64_t seed) {
   const bool f32 = check_act_or_f32(out, "out");
   TORCH_CHECK(out.numel() % Cpad == 0, "hcb.synth_images: numel % Cpad");
@@ -1125,16 +1141,9 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
                           const c10::optional<Tensor>& stats_shift, bool y_planes = false) {
   const int64_t xps = check_planes(x, "x");
   TORCH_CHECK(cfg >= 0 && cfg < hcb::N_P3_CFG, "hcb.conv_p3: cfg 0..36");
-  // conv_params validates geometry and byte ranges on plane 0 (a bf16 tensor of this build's type);
-  // split-K is validated here against the p3 tiles
-  std::vector<int64_t> g1(g.begin(), g.end());
-  const int64_t splits = g1.size() > 30 ? g1[30] : 1;
-  if (g1.size() > 30) g1[30] = 1;
-  hcb::ConvParams p = conv_params(x.select(0, 0), w, y, yres, bias, c10::nullopt, g1, 0);
+  // conv_params validates geometry and byte ranges on plane 0 (a bf16 tensor of this build's type)
+  hcb::ConvParams p = conv_params(x.select(0, 0), w, y, yres, bias, g);
   const int bm = hcb::p3_tile_m((int)cfg), bn = hcb::p3_tile_n((int)cfg);
-  const int64_t tiles = (int64_t)((p.M + bm - 1) / bm) * ((p.Nout + bn - 1) / bn);
-  p.splits = (int)splits;
-  TORCH_CHECK(p.splits >= 1 && p.splits <= p.Kpad / 64, "hcb.conv_p3: 1 <= splits <= k-steps");
   TORCH_CHECK(y_planes ? !p.out_f32 : p.out_f32 && y.scalar_type() == at::kFloat,
               "hcb.conv_p3: fp32 output (geom out_f32 = 0 with a plane output)");
   check_range(x, 2 * xps * 2 + (int64_t)p.x_bytes, "x planes");
@@ -1148,23 +1157,10 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
   check_align16(l.data_ptr(), "w_lo[1]");
   p.w_lo = m.data_ptr();
   p.w_lo2 = l.data_ptr();
-  p.stats = nullptr;
-  if (stats.has_value()) {
-    check_f32(*stats, "stats");
-    const int tiles_m = (p.M + hcb::p3_tile_m((int)cfg) - 1) / hcb::p3_tile_m((int)cfg);
-    const int64_t rows = p.stats_R > 0 ? p.stats_R : tiles_m;
-    TORCH_CHECK(stats->numel() >= rows * 2 * p.Nout, "hcb.conv_p3: stats buffer too small");
-    p.stats = stats->data_ptr<float>();
-  }
+  attach_stats(p, stats, bm, "conv_p3");
   TORCH_CHECK(!stats_shift.has_value() || p.stats != nullptr, "hcb.conv_p3: stats_shift without stats");
   p.stats_shift = opt_f32(stats_shift, p.Nout, "stats_shift");
-  if (p.splits > 1) {
-    TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.conv_p3: split-K workspace not set");
-    TORCH_CHECK(tiles * p.splits * bm * bn * 4 <= g_splitk_ws_bytes, "hcb.conv_p3: split-K workspace too small");
-    TORCH_CHECK(tiles <= g_splitk_cnt_n, "hcb.conv_p3: split-K counter array too small");
-    p.ws = g_splitk_ws;
-    p.cnt = g_splitk_cnt;
-  }
+  attach_splitk(p, bm, bn, "conv_p3");
   if (hcb::p3_cfg_streamk((int)cfg)) {  // stream-K (conv_p3_persist.h): the launcher sizes its shares against the workspace
     TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.conv_p3: stream-K needs the split-K workspace");
     p.ws = g_splitk_ws;
@@ -1200,22 +1196,22 @@ void conv_p3_inf(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Ten
                  const c10::optional<Tensor>& res, at::IntArrayRef g, int64_t cfg, const Tensor& gamma,
                  const Tensor& beta, const Tensor& mean, const Tensor& var, double eps) {
   TORCH_CHECK(hcb::p3_cfg_has_inf((int)cfg), "hcb.conv_p3_inf: cfg 0..17 (a persistent cfg runs its per-tile twin)");
-  TORCH_CHECK(g.size() >= 28, "hcb.conv_p3_inf: geom");
+  const hcb::ConvParams q = decode_geom(kConvGeom, g, "conv_p3_inf");
   const bool yp3 = y.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(yp3 == (g[27] == 0), "hcb.conv_p3_inf: geom out_f32 = 0 exactly for a plane output");
+  TORCH_CHECK(yp3 == (q.out_f32 == 0), "hcb.conv_p3_inf: geom out_f32 = 0 exactly for a plane output");
   hcb::ConvParams p;
   if (yp3) {
     const int64_t yps = check_planes(y, "y");
     c10::optional<Tensor> r0;
     int64_t rps = 0;
-    if (g[26]) {
+    if (q.beta) {
       TORCH_CHECK(res.has_value(), "hcb.conv_p3_inf: beta needs res");
       rps = check_planes(*res, "res");
       r0 = res->select(0, 0);
     }
     p = p3_params(x, w, w_lo, y.select(0, 0), r0, c10::nullopt, c10::nullopt, g, cfg, c10::nullopt, true);
     // conv_params checked plane 0's rows against the storage; the other two planes lie 2 * stride on
-    const int64_t span = ((int64_t)(p.M - 1) * p.ldy + ((p.Nout + 7) / 8) * 8) * 2;
+    const int64_t span = out_span_bytes(p.M, p.ldy, p.Nout, 2);
     check_range(y, 2 * yps * 2 + span, "y planes");
     TORCH_CHECK(yps >= span / 2, "hcb.conv_p3_inf: y planes overlap");
     if (p.beta) check_range(*res, 2 * rps * 2 + span, "res planes");
@@ -1223,7 +1219,7 @@ void conv_p3_inf(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Ten
     p.y_plane = yps;
     p.yres_plane = rps;
   } else {
-    TORCH_CHECK(!g[26] || (res.has_value() && res->scalar_type() == at::kFloat), "hcb.conv_p3_inf: fp32 res");
+    TORCH_CHECK(!q.beta || (res.has_value() && res->scalar_type() == at::kFloat), "hcb.conv_p3_inf: fp32 res");
     p = p3_params(x, w, w_lo, y, res, c10::nullopt, c10::nullopt, g, cfg, c10::nullopt);
   }
   set_inf(p, y, gamma, beta, mean, var, eps);
@@ -1233,43 +1229,15 @@ void conv_p3_inf(const Tensor& x, const Tensor& w, const Tensor& w_lo, const Ten
 // geom as conv_wgrad; dy / x planes
 void conv_wgrad_p3(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArrayRef g, int64_t cfg,
                    int64_t splits) {
-  TORCH_CHECK(g.size() == 17, "hcb.conv_wgrad_p3: geom must have 17 entries");
   const int64_t dps = check_planes(dy, "dy"), xps = check_planes(x, "x");
   TORCH_CHECK(cfg >= 0 && cfg < hcb::N_WP3_CFG, "hcb.conv_wgrad_p3: cfg 0..18");
-  check_f32(dw, "dw");
-  hcb::WgradParams p{};
-  p.N = g[0]; p.H = g[1]; p.W = g[2]; p.C = g[3]; p.ldx = g[4];
-  p.P = g[5]; p.Q = g[6]; p.R = g[7]; p.S = g[8];
-  p.stride_h = g[9]; p.stride_w = g[10]; p.pad_h = g[11]; p.pad_w = g[12];
-  p.dil_h = g[13]; p.dil_w = g[14];
-  p.Nout = g[15]; p.ldy = g[16];
-  p.K = p.R * p.S * p.C;
-  p.M = p.N * p.P * p.Q;
-  TORCH_CHECK(p.C % 8 == 0 && p.ldx % 8 == 0, "hcb.conv_wgrad_p3: C, ldx multiples of 8");
-  TORCH_CHECK(p.ldy % 8 == 0 && p.ldy >= p.Nout, "hcb.conv_wgrad_p3: bad ldy");
-  TORCH_CHECK(splits >= 1, "hcb.conv_wgrad_p3: splits >= 1");
-  const int64_t xb = x_span_bytes(p.N, p.H, p.W, p.C, p.ldx, 2);
-  const int64_t yb = ((int64_t)p.M - 1) * p.ldy * 2 + (int64_t)((p.Nout + 7) / 8) * 8 * 2;
-  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31), "hcb.conv_wgrad_p3: operand exceeds 2 GiB");
+  hcb::WgradParams p;
+  const int eff_splits = wgrad_params(p, dy, x, dw, g, splits, "conv_wgrad_p3");
   TORCH_CHECK(2 * xps * 2 < (1ll << 32) && 2 * dps * 2 < (1ll << 32), "hcb.conv_wgrad_p3: plane stride range");
-  check_range(x, 2 * xps * 2 + xb, "x planes");
-  check_range(dy, 2 * dps * 2 + yb, "dy planes");
-  check_range(dw, (int64_t)p.Nout * p.K * 4, "dw");
+  check_range(x, 2 * xps * 2 + (int64_t)p.x_bytes, "x planes");
+  check_range(dy, 2 * dps * 2 + (int64_t)p.dy_bytes, "dy planes");
   TORCH_CHECK(!hcb::wp3_cfg_persistent((int)cfg) || (int64_t)p.Nout * p.K * 4 < (1ll << 31),
               "hcb.conv_wgrad_p3: the persistent configs address dW through a 32-bit buffer offset");
-  const int nkt = (p.M + 63) / 64;
-  const int per = (nkt + (int)splits - 1) / (int)splits;
-  p.ksteps_per_split = per;
-  const int eff_splits = (nkt + per - 1) / per;
-  p.fd_pq = hcb::make_fastdiv((uint32_t)(p.P * p.Q));
-  p.fd_q = hcb::make_fastdiv((uint32_t)p.Q);
-  p.fd_c = hcb::make_fastdiv((uint32_t)p.C);
-  p.fd_s = hcb::make_fastdiv((uint32_t)p.S);
-  p.dy = dy.data_ptr();
-  p.x = x.data_ptr();
-  p.dw = dw.data_ptr<float>();
-  p.dy_bytes = (uint32_t)yb;
-  p.x_bytes = (uint32_t)xb;
   p.dy_plane = (uint32_t)(dps * 2);
   p.x_plane = (uint32_t)(xps * 2);
   hcb::launch_wgrad_p3(p, (int)cfg, eff_splits, cur_stream());
@@ -1314,11 +1282,11 @@ void set_deterministic(bool on) { hcb::set_deterministic(on); }
 
 
 HCB_TORCH_LIBRARY(hcb, m) {
-  m.def("conv_igemm(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, Tensor? bias, Tensor(b!)? stats, int[] geom, int cfg, Tensor? stats_shift=None, Tensor? w_lo=None) -> ()");
+  m.def("conv_igemm(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, Tensor? bias, Tensor(b!)? stats, int[] geom, int cfg, Tensor? stats_shift=None) -> ()");
   m.def("conv_igemm_bnb(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, int[] geom, int cfg, Tensor z, Tensor? yact, int ld, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor(b!) acc, int R, int mode) -> ()");
   m.def("conv_igemm_inf(Tensor x, Tensor w, Tensor(a!) y, Tensor? res, int[] geom, int cfg, Tensor gamma, Tensor beta, Tensor mean, Tensor var, float eps) -> ()");
-  m.def("conv_tiles_m(int M, int cfg) -> int", conv_tiles_m);
   m.def("gemm_cfg_table(str family) -> int[]", gemm_cfg_table);
+  m.def("conv_geom_fields(str kind) -> str[]", conv_geom_fields);
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
   m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);
   m.def("conv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int[] geom, int cfg, int splits) -> ()");
@@ -1340,15 +1308,12 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("adam(Tensor(a!) w, Tensor(b!) m, Tensor(c!) v, Tensor g, int n_decay, Tensor hyper, Tensor ohyper, Tensor state, Tensor(d!)? l2) -> ()");
   m.def("adam_advance(Tensor(a!) state, Tensor ohyper, Tensor hyper) -> ()");
   m.def("weight_pack(Tensor master, Tensor(a!) pack, Tensor table, int max_work, int lo=0) -> ()");
-  m.def("cast_f32_bf16(Tensor x, Tensor(a!) y) -> ()");
   m.def("add_bf16(Tensor a, Tensor b, Tensor(a!) y) -> ()");
-  m.def("scale_f32(Tensor(a!) x, float s) -> ()");
   m.def("relu_bwd(Tensor dy, Tensor y, Tensor(a!) dz) -> ()");
   m.def("bn_apply_acc(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor acc, int R, float eps, float momentum, Tensor gamma, Tensor beta, int relu, Tensor(b!) saved_mean, Tensor(c!) saved_invstd, Tensor(d!)? running_mean, Tensor(e!)? running_var, Tensor? shift=None, Tensor? res_acc=None, Tensor? res_gamma=None, Tensor? res_beta=None, Tensor(g!)? res_saved_mean=None, Tensor(h!)? res_saved_invstd=None, Tensor(i!)? res_running_mean=None, Tensor(j!)? res_running_var=None, Tensor? res_shift=None) -> ()");
   m.def("bn_bwd_reduce_acc(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu, Tensor(a!) acc, int R, Tensor(b!)? gout, int ldg, Tensor? pool_amax=None, int[]? pool_geom=None) -> ()");
   m.def("bn_bwd_apply_acc(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, Tensor(a!) dx, int lddx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor acc, int R, Tensor(b!) dgamma, Tensor(c!) dbeta, int relu, Tensor(d!)? shift_out=None, Tensor? pool_amax=None, int[]? pool_geom=None, Tensor? add=None, int ldadd=0) -> ()");
   m.def("bn_stats_acc(Tensor x, int ldx, int M, int C, Tensor(a!) acc, int R, Tensor? shift=None) -> ()");
-  m.def("l2norm_sq(Tensor x, Tensor(a!) out) -> ()");
   m.def("preprocess_images(Tensor src, Tensor desc, Tensor desc_host, Tensor(a!) out, float[] scale, float[] bias) -> ()");
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
@@ -1396,15 +1361,12 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("adam", adam);
   m.impl("adam_advance", adam_advance);
   m.impl("weight_pack", weight_pack);
-  m.impl("cast_f32_bf16", cast_f32_bf16);
   m.impl("add_bf16", add_bf16);
-  m.impl("scale_f32", scale_f32);
   m.impl("relu_bwd", relu_bwd);
   m.impl("bn_apply_acc", bn_apply_acc);
   m.impl("bn_bwd_reduce_acc", bn_bwd_reduce_acc);
   m.impl("bn_bwd_apply_acc", bn_bwd_apply_acc);
   m.impl("bn_stats_acc", bn_stats_acc);
-  m.impl("l2norm_sq", l2norm_sq);
   m.impl("synth_images", synth_images);
   m.impl("dropout_fwd", dropout_fwd);
   m.impl("bn_relu_maxpool_acc", bn_relu_maxpool_acc);

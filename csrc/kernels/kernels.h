@@ -257,12 +257,9 @@ void launch_dropout_fwd(const void* x, void* y, uint8_t* mask, int64_t n, float 
                         const int64_t* step, hipStream_t st, bool f32 = false);
 void launch_dropout_bwd(const void* dy, const uint8_t* mask, void* dx, int64_t n, float keep, hipStream_t st,
                         bool f32 = false);
-void launch_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st);
 void launch_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t st);
 void launch_add_bf16(const void* a, const void* b, void* y, int64_t n, hipStream_t st);
-void launch_scale_f32(float* x, int64_t n, float s, hipStream_t st);
 void launch_relu_bwd(const void* dy, const void* y, void* dz, int64_t n, hipStream_t st, bool f32 = false);
-void launch_l2norm_sq(const float* x, int64_t n, float* out, hipStream_t st);
 
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,

@@ -367,19 +367,6 @@ __global__ void adam_advance_kernel(float* state, const float* ohyper, const flo
   state[1] *= ohyper[1];
 }
 
-__global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ x, int64_t n,
-                                                     float* out) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    s += x[i] * x[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
-}
-
 // ------------------------------------------------------------------ weights
 // Per entry the work is (A) the row-padded copy [Nout][K] -> [Nout][Kpad] in 8-element vectors
 // (two 16-byte reads, one 16-byte write per lane; pad columns stay zero from allocation) and
@@ -529,11 +516,6 @@ __global__ __launch_bounds__(256) void dropout_bwd_kernel(const T* __restrict__ 
   }
 }
 
-__global__ void cast_f32_bf16_kernel(const float* x, uint16_t* y, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    y[i] = f2act(x[i]);
-}
 __global__ void cast_bf16_f32_kernel(const uint16_t* x, float* y, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
@@ -565,12 +547,6 @@ __global__ void relu_bwd_kernel(const T* dy, const T* y, T* dz, int64_t n8) {
     for (int e = 0; e < 8; ++e) d[e] = v[e] > 0.f ? d[e] : 0.f;
     Act8<T>::store(dz + i * 8, d);
   }
-}
-
-__global__ void scale_f32_kernel(float* x, int64_t n, float s) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    x[i] *= s;
 }
 
 // ------------------------------------------------------------------ synthetic data
@@ -814,9 +790,6 @@ void launch_adam(float* w, float* m, float* v, const float* g, int64_t n, int64_
 void launch_adam_advance(float* state, const float* ohyper, const float* hyper, int hyper_n, hipStream_t st) {
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, state, ohyper, hyper, hyper_n);
 }
-void launch_l2norm_sq(const float* x, int64_t n, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(l2norm_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, out);
-}
 void launch_weight_pack(const float* master, uint16_t* pack, const WPackEntry* entries_dev,
                         int n_entries, int64_t max_work, hipStream_t st, int lo, int64_t pstride) {
   int64_t units = max_work / 2048 + 2;  // A chunks are 2048 elements, B tiles 4096
@@ -847,9 +820,6 @@ void launch_dropout_bwd(const void* dy, const uint8_t* mask, void* dx, int64_t n
     hipLaunchKernelGGL(dropout_bwd_kernel<uint16_t>, dim3(grid_for(n / 8)), dim3(256), 0, st, (const uint16_t*)dy,
                        mask, (uint16_t*)dx, n / 8, 1.f / keep);
 }
-void launch_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st) {
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, n);
-}
 void launch_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t st) {
   hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, n);
 }
@@ -864,9 +834,6 @@ void launch_relu_bwd(const void* dy, const void* y, void* dz, int64_t n, hipStre
   else
     hipLaunchKernelGGL(relu_bwd_kernel<uint16_t>, dim3(grid_for(n / 8)), dim3(256), 0, st, (const uint16_t*)dy,
                        (const uint16_t*)y, (uint16_t*)dz, n / 8);
-}
-void launch_scale_f32(float* x, int64_t n, float s, hipStream_t st) {
-  hipLaunchKernelGGL(scale_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, s);
 }
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32) {
