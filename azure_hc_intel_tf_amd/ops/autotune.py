@@ -43,6 +43,8 @@ def _entry_valid(key, val) -> bool:
     tiles = {"fwd": Fn._CONV_TILES, "dgb": Fn._CONV_TILES, "wgrad": Fn._WGRAD_TILES, "fwd3": Fn._P3_TILES,
              "wgrad3": Fn._WP3_TILES}.get(key[0])
     cfg, splits = (val[0], val[1]) if isinstance(val, (tuple, list)) else (val, 1)
+    if key[0] == "fwd3" and int(cfg) in Fn._P3_PATCH_TILES:  # the 3x3 patch kernels: 9 taps, no split-K
+        return key[4] == 9 and int(splits) == 1
     return tiles is not None and int(cfg) in tiles and int(splits) >= 1
 
 
@@ -224,12 +226,17 @@ def layer_problems_p3(layer, batch: int, dev) -> List[Tuple]:
             buf["dw"] = torch.zeros((Cout, spec.K), dtype=torch.float32, device=dev)
         return buf
 
-    out = [(Fn.fwd3_key(M, Cout, spec.K, taps), [list(c) for c in Fn.p3_candidates(M, Cout, spec.K)],
+    # 3x3 / stride 1 / same-size convs (and their data gradients): also the patch-resident kernels
+    same = spec.sh == 1 and spec.sw == 1 and (P, Q) == (H, W)
+    patch = (lambda m, n, k: Fn.p3_patch_candidates(m, n, k, taps, H, W)) if same else (lambda m, n, k: [])
+    out = [(Fn.fwd3_key(M, Cout, spec.K, taps),
+            [list(c) for c in Fn.p3_candidates(M, Cout, spec.K) + patch(M, Cout, spec.K)],
             lambda plan: Fn.conv_forward(ops()["x"], spec, layer.pack.pack, None, ops()["y"], stats=ops()["acc"],
                                          cfg=plan, stats_R=8))]
     if layer.need_dx:
         if not phases:
-            out.append((Fn.fwd3_key(geo[0], Cin, geo[1], taps), [list(c) for c in Fn.p3_candidates(geo[0], Cin, geo[1])],
+            out.append((Fn.fwd3_key(geo[0], Cin, geo[1], taps),
+                        [list(c) for c in Fn.p3_candidates(geo[0], Cin, geo[1]) + patch(geo[0], Cin, geo[1])],
                         lambda plan: Fn.conv_dgrad(ops()["dz"], spec, layer.pack.tr, None, ops()["dx"], False,
                                                    cfg=plan)))
         for ph in phases:

@@ -585,6 +585,38 @@ _P3_PERSIST = {18: 15, 19: 14, 20: 16, 21: 17, 22: 7, 23: 15, 24: 14, 25: 16, 26
 _P3_BRES = {31: 3, 32: 2, 33: 3, 34: 2, 35: 2, 36: 2}
 
 
+# the 3x3 / stride 1 / pad 1 kernels with the input patch resident in LDS (conv_p3_patch.h, gemm_cfg.h
+# HCB_P3PATCH_CFGS: a table of its own, numbered from 64): cfg -> block tile, and -> the per-tile cfg of
+# that block tile their launcher runs for a problem they do not serve. No split-K, no inference epilogue.
+_P3_PATCH_TILES = {64: (128, 128)}
+_P3_PATCH_FB = {64: 8}
+_P3_PATCH_NST = 3
+
+
+def p3_patch_rows(H: int, W: int, bm: int) -> int:
+    """Rows of one patch buffer (gemm_cfg.h p3_patch_rows): the padded span of bm consecutive output
+    pixels, rounded up to the 16 rows one wave's LDS-DMA instruction fills."""
+    d = bm - 1
+    span = d + (d + W - 1) // W + (W + 1) * ((d + H * W - 1) // (H * W)) + 2 * (W + 1) + 3
+    return -(-span // 16) * 16
+
+
+def p3_patch_fits(cfg: int, H: int, W: int, bnb: bool = True) -> bool:
+    """Whether a patch cfg's ring, two patch buffers and BN-backward parameters fit the 160 KB of LDS
+    on H x W images (gemm_cfg.h p3_patch_lds); its launcher runs the fallback otherwise."""
+    bm, bn = _P3_PATCH_TILES[cfg]
+    lds = _P3_PATCH_NST * 3 * bn * 64 + 2 * 3 * p3_patch_rows(H, W, bm) * 64 + 1024 + (bn * 16 if bnb else 0)
+    return lds <= 160 * 1024
+
+
+def p3_patch_candidates(M: int, N: int, K: int, taps: int, H: int, W: int):
+    """(cfg, 1) of the patch kernels worth timing for a 3x3 / stride 1 / pad 1 problem on H x W images."""
+    if taps != 9 or K % (9 * 32) != 0:
+        return []
+    return [(c, 1) for c, (bm, bn) in _P3_PATCH_TILES.items()
+            if not (N <= 64 and bn > 64) and p3_patch_fits(c, H, W)]
+
+
 def p3_bres_fits(cfg: int, N: int, K: int) -> bool:
     """Whether a B-resident cfg serves an (N, K) problem (else its launcher falls back)."""
     bm, bn = _P3_TILES[cfg]
@@ -1008,7 +1040,7 @@ def conv_bn_inference(x, spec: ConvSpec, wpack, w_master, gamma, beta, running_m
             residual = to_planes(residual) if is_planes(out) else from_planes(residual)
     cfg, splits = _plan(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw, **(_P3_PLAN if p3 else {}))
     if p3:
-        cfg = _P3_PERSIST.get(cfg, cfg)
+        cfg = _P3_PERSIST.get(_P3_PATCH_FB.get(cfg, cfg), _P3_PATCH_FB.get(cfg, cfg))
     elif cfg in PATCH_CFGS:  # no split-K on the twin, as launch_conv_igemm's own fallback
         cfg, splits = _PATCH_TWIN[cfg], 1
     if residual is not None:

@@ -368,6 +368,15 @@ void conv_igemm_inf(const Tensor& x, const Tensor& w, const Tensor& y, const c10
 
 // the rows of a family's table (gemm_cfg.h), flat, 12 per cfg: cfg, kind, WM, WN, TM, TN, slot depth,
 // ring slots, occupancy, PMAX / KS, fallback cfg (-1 none), has an inference-epilogue instantiation
+// host-only: the LDS bytes a plane 3x3 patch cfg needs on H x W images (gemm_cfg.h p3_patch_lds;
+// its launcher runs the row's fallback above P3_PATCH_LDS_MAX) and the patch rows of one buffer
+std::vector<int64_t> p3_patch_fit(int64_t cfg, int64_t H, int64_t W, bool bnb) {
+  TORCH_CHECK(hcb::p3_cfg_patch((int)cfg) && H >= 1 && W >= 1 && H < 32768 && W < 32768, "hcb.p3_patch_fit: a patch cfg, H, W >= 1");
+  const int bm = hcb::p3_tile_m((int)cfg);
+  return {(int64_t)hcb::p3_patch_cfg_lds((int)cfg, (int)H, (int)W, bnb), (int64_t)hcb::p3_patch_rows((int)H, (int)W, bm),
+          (int64_t)hcb::P3_PATCH_LDS_MAX};
+}
+
 std::vector<int64_t> gemm_cfg_table(std::string family) {
   const hcb::GemmCfg* rows = nullptr;
   int n = 0;
@@ -380,8 +389,10 @@ std::vector<int64_t> gemm_cfg_table(std::string family) {
     rows = hcb::P3_CFGS, n = hcb::N_P3_CFG, inf = hcb::p3_cfg_has_inf;
   } else if (family == "wgrad_p3") {
     rows = hcb::WP3_CFGS, n = hcb::N_WP3_CFG;
+  } else if (family == "p3_patch") {
+    rows = hcb::P3PATCH_CFGS, n = hcb::N_P3PATCH_CFG;
   } else {
-    TORCH_CHECK(false, "hcb.gemm_cfg_table: family is conv, wgrad, p3 or wgrad_p3");
+    TORCH_CHECK(false, "hcb.gemm_cfg_table: family is conv, wgrad, p3, wgrad_p3 or p3_patch");
   }
   std::vector<int64_t> out;
   for (int i = 0; i < n; ++i) {
@@ -1140,7 +1151,7 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
                           const c10::optional<Tensor>& stats, at::IntArrayRef g, int64_t cfg,
                           const c10::optional<Tensor>& stats_shift, bool y_planes = false) {
   const int64_t xps = check_planes(x, "x");
-  TORCH_CHECK(cfg >= 0 && cfg < hcb::N_P3_CFG, "hcb.conv_p3: cfg 0..36");
+  TORCH_CHECK(hcb::p3_cfg_valid((int)cfg), "hcb.conv_p3: cfg 0..36, or a 3x3 patch cfg (64..)");
   // conv_params validates geometry and byte ranges on plane 0 (a bf16 tensor of this build's type)
   hcb::ConvParams p = conv_params(x.select(0, 0), w, y, yres, bias, g);
   const int bm = hcb::p3_tile_m((int)cfg), bn = hcb::p3_tile_n((int)cfg);
@@ -1286,6 +1297,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("conv_igemm_bnb(Tensor x, Tensor w, Tensor(a!) y, Tensor? yres, int[] geom, int cfg, Tensor z, Tensor? yact, int ld, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor(b!) acc, int R, int mode) -> ()");
   m.def("conv_igemm_inf(Tensor x, Tensor w, Tensor(a!) y, Tensor? res, int[] geom, int cfg, Tensor gamma, Tensor beta, Tensor mean, Tensor var, float eps) -> ()");
   m.def("gemm_cfg_table(str family) -> int[]", gemm_cfg_table);
+  m.def("p3_patch_fit(int cfg, int H, int W, bool bnb) -> int[]", p3_patch_fit);
   m.def("conv_geom_fields(str kind) -> str[]", conv_geom_fields);
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
   m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);

@@ -10,6 +10,8 @@
 // §2.6, driven by /root/reference/benchmark-scripts/run-tf-sing-ucx-openmpi.sh:62-81):
 //   * conv_igemm_p3_kernel  forward and data-gradient implicit GEMMs (fp32 output, fused BN
 //                           statistics, beta-accumulate, split-K via splitk_gather)
+//   * conv_p3_patch_kernel  the 3x3 / stride 1 forward and data gradient with the input patch
+//                           resident in LDS (conv_p3_patch.h)
 //   * conv_wgrad_p3_kernel  weight-gradient implicit GEMM (transposed fragment reads,
 //                           ds_read_b64_tr_b16, split-K with fp32 atomics)
 //
@@ -19,6 +21,7 @@
 // workgroup per CU). Each stage carries 6x the MFMA time of a bf16 k-step (1536 cycles per wave at
 // 64x32 wave tiles), which covers the next stage's DMA latency, so double buffering is enough.
 #include "conv_p3_fwd.h"
+#include "conv_p3_patch.h"
 #include "conv_p3_persist.h"
 #include "conv_p3_wgrad.h"
 
@@ -55,6 +58,7 @@ void launch_conv_p3(const ConvParams& p, int cfg, hipStream_t st) {
     launch_p3_cfg<false, true>(p, cfg, st);
     return;
   }
+  if (p3_cfg_patch(cfg) && (cfg = launch_p3_patch_cfg(p, cfg, st)) < 0) return;
   if (cfg >= 0 && (cfg = launch_p3_persist(p, cfg, st)) < 0) return;
   if (p.bnb_acc != nullptr)
     launch_p3_cfg<true, false>(p, cfg, st);

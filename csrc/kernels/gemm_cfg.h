@@ -24,6 +24,7 @@ enum GemmKind {
   K_STREAMK = 6,  // ... its stream-K form
   K_BRES = 7,     // ... with the workgroup's weight slice resident in LDS
   K_RETIRED = 8,  // a stream-K number kept for old plans: runs FB
+  K_P3PATCH = 9,  // plane GEMM, 3x3 / stride 1 with the input patch resident in LDS (conv_p3_patch.h)
 };
 
 // ---------------------------------------------------------------- 16-bit forward / data gradient
@@ -124,6 +125,16 @@ enum GemmKind {
   X(35, BRES, 4, 2, 32, 32, 32, 2, 1, 19)       \
   X(36, BRES, 4, 2, 32, 64, 32, 2, 1, 22)
 
+// ---------------------------------------------------------------- plane (fp32) 3x3 patch kernels
+// X(cfg, KIND, WM, WN, TM, TN, KW, NST, OCC, FB): a table of its own, numbered from P3_PATCH_CFG0, so
+// that every number of HCB_P3_CFGS (and of tuned/*.json) keeps its meaning. A problem the kernel does
+// not serve (not 3x3 / stride 1 / pad 1, C % 32, split-K, a patch that does not fit LDS) runs FB, the
+// per-tile cfg of the same block tile.
+constexpr int P3_PATCH_CFG0 = 64;
+// (measured and not kept: the 2x4 waves of 64x32 form of 64, equal to it; a 128x64 tile of four waves
+// for the 64-column stage-1 layers, 33 % slower than their persistent cfg: profiles/p3_patch.txt)
+#define HCB_P3PATCH_CFGS(X) X(64, P3PATCH, 4, 2, 32, 64, 32, 3, 1, 8)
+
 // ---------------------------------------------------------------- plane (fp32) weight gradient
 // X(cfg, KIND, WM, WN, TM, TN, KW, NST, OCC): NST slots of KW pixel rows. 16-18: persistent twins of
 // 12, 13, 15 (their ring is always 2 x 32).
@@ -163,6 +174,7 @@ inline constexpr GemmCfg CONV_CFGS[] = {HCB_CONV_CFGS(HCB_ROW_CONV)};
 inline constexpr GemmCfg WGRAD_CFGS[] = {HCB_WGRAD_CFGS(HCB_ROW_WGRAD)};
 inline constexpr GemmCfg P3_CFGS[] = {HCB_P3_CFGS(HCB_ROW_P3)};
 inline constexpr GemmCfg WP3_CFGS[] = {HCB_WP3_CFGS(HCB_ROW_WP3)};
+inline constexpr GemmCfg P3PATCH_CFGS[] = {HCB_P3PATCH_CFGS(HCB_ROW_P3)};
 #undef HCB_ROW_CONV
 #undef HCB_ROW_WGRAD
 #undef HCB_ROW_P3
@@ -182,6 +194,22 @@ constexpr int N_CONV_CFG = sizeof(CONV_CFGS) / sizeof(GemmCfg);
 constexpr int N_WGRAD_CFG = sizeof(WGRAD_CFGS) / sizeof(GemmCfg);
 constexpr int N_P3_CFG = sizeof(P3_CFGS) / sizeof(GemmCfg);
 constexpr int N_WP3_CFG = sizeof(WP3_CFGS) / sizeof(GemmCfg);
+constexpr int N_P3PATCH_CFG = sizeof(P3PATCH_CFGS) / sizeof(GemmCfg);
+
+// row i of the patch table is cfg P3_PATCH_CFG0 + i and falls back to a per-tile plane cfg of its block tile
+constexpr bool p3_patch_rows_ok() {
+  for (int i = 0; i < N_P3PATCH_CFG; ++i) {
+    const GemmCfg& r = P3PATCH_CFGS[i];
+    if (r.cfg != P3_PATCH_CFG0 + i || r.fb < 0 || r.fb >= N_P3_CFG || r.kw != 32) return false;
+    const GemmCfg& f = P3_CFGS[r.fb];
+    if (f.kind != K_TILE || f.wm * f.tm != r.wm * r.tm || f.wn * f.tn != r.wn * r.tn) return false;
+  }
+  return true;
+}
+static_assert(p3_patch_rows_ok(), "a patch row falls back to the per-tile cfg of the same block tile");
+constexpr bool p3_cfg_patch(int cfg) { return cfg >= P3_PATCH_CFG0 && cfg < P3_PATCH_CFG0 + N_P3PATCH_CFG; }
+// a cfg the plane forward / data-gradient launcher accepts
+constexpr bool p3_cfg_valid(int cfg) { return (cfg >= 0 && cfg < N_P3_CFG) || p3_cfg_patch(cfg); }
 
 // a cfg's launcher kind (-1 outside the table) and block tile (d outside the table)
 template <int N>
@@ -196,8 +224,12 @@ constexpr int conv_tile_m(int cfg) { return gemm_tile(CONV_CFGS, cfg, false, 128
 constexpr int conv_tile_n(int cfg) { return gemm_tile(CONV_CFGS, cfg, true, 128); }
 constexpr int wgrad_tile_m(int cfg) { return gemm_tile(WGRAD_CFGS, cfg, false, 64); }
 constexpr int wgrad_tile_n(int cfg) { return gemm_tile(WGRAD_CFGS, cfg, true, 64); }
-constexpr int p3_tile_m(int cfg) { return gemm_tile(P3_CFGS, cfg, false, 128); }
-constexpr int p3_tile_n(int cfg) { return gemm_tile(P3_CFGS, cfg, true, 64); }
+constexpr int p3_tile_m(int cfg) {
+  return p3_cfg_patch(cfg) ? gemm_tile(P3PATCH_CFGS, cfg - P3_PATCH_CFG0, false, 128) : gemm_tile(P3_CFGS, cfg, false, 128);
+}
+constexpr int p3_tile_n(int cfg) {
+  return p3_cfg_patch(cfg) ? gemm_tile(P3PATCH_CFGS, cfg - P3_PATCH_CFG0, true, 64) : gemm_tile(P3_CFGS, cfg, true, 64);
+}
 constexpr int p3_slot_k(int cfg) { return cfg >= 0 && cfg < N_P3_CFG ? P3_CFGS[cfg].kw : 32; }
 constexpr int wgrad_p3_tile_m(int cfg) { return gemm_tile(WP3_CFGS, cfg, false, 64); }
 constexpr int wgrad_p3_tile_n(int cfg) { return gemm_tile(WP3_CFGS, cfg, true, 64); }
@@ -213,5 +245,29 @@ constexpr bool p3_cfg_streamk(int cfg) {
   return gemm_kind(P3_CFGS, cfg) == K_STREAMK || gemm_kind(P3_CFGS, cfg) == K_RETIRED;
 }
 constexpr bool wp3_cfg_persistent(int cfg) { return gemm_kind(WP3_CFGS, cfg) == K_PERSIST; }
+
+// ---------------------------------------------------------------- the resident 3x3 patch (conv_p3_patch.h)
+// The patch is addressed by a padded linear index with ONE shared zero row between images and ONE
+// shared zero column between image rows: Lp(n, p, q) = (n * (H + 1) + p) * (W + 1) + q, and tap (r, s)
+// of output pixel (n, p, q) reads row Lp + r * (W + 1) + s. Upper bound of the rows a block of BM
+// consecutive output pixels spans: BM - 1 steps, +1 per image-row wrap, +(W + 1) per image wrap, plus
+// the window's reach 2 * (W + 1) + 3; rounded up to the 16 rows one wave's LDS-DMA instruction fills.
+constexpr int p3_patch_rows(int H, int W, int BM) {
+  const int d = BM - 1, span = d + (d + W - 1) / W + (W + 1) * ((d + H * W - 1) / (H * W)) + 2 * (W + 1) + 3;
+  return (span + 15) / 16 * 16;
+}
+// LDS bytes of a launch: NST weight slots of three BN x 64-byte planes, two patch buffers of three
+// planes of 64-byte rows, a 1 KB landing zone for the DMA pieces past the patch, the fused BN-backward
+// parameters (16 bytes per column)
+constexpr long p3_patch_lds(int H, int W, int BM, int BN, int NST, bool bnb) {
+  return (long)NST * 3 * BN * 64 + 2l * 3 * p3_patch_rows(H, W, BM) * 64 + 1024 + (bnb ? BN * 16 : 0);
+}
+// of patch cfg `cfg` on H x W images; 0: not a patch cfg
+constexpr long p3_patch_cfg_lds(int cfg, int H, int W, bool bnb) {
+  if (!p3_cfg_patch(cfg)) return 0;
+  const GemmCfg& r = P3PATCH_CFGS[cfg - P3_PATCH_CFG0];
+  return p3_patch_lds(H, W, r.wm * r.tm, r.wn * r.tn, r.nst, bnb);
+}
+constexpr long P3_PATCH_LDS_MAX = 160 * 1024;
 
 }  // namespace hcb
