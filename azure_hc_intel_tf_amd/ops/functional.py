@@ -1267,9 +1267,9 @@ def pool_backward(dy, x, y, dx, kh, kw, sh, sw, pads, is_max, incl_pad=False, ac
             x = dx
     if native(x):
         # the kernel walks x / dx with one pixel stride and y / dy with another: align views
-        if ld(y) != ld(dy):
-            y = y.contiguous() if ld(dy) == y.shape[3] else y
-            dy = dy.contiguous() if ld(y) != ld(dy) else dy
+        if ld(y) != ld(dy):  # a window of a wider buffer is copied; windows of two widths: both
+            dy = dy.contiguous() if ld(dy) != dy.shape[3] else dy
+            y = y.contiguous() if ld(y) != ld(dy) else y
         if ld(dx) != ld(x):
             tmp = dx.contiguous() if accumulate else torch.empty(dx.shape, dtype=dx.dtype, device=dx.device)
             xc = x.contiguous()
