@@ -198,6 +198,9 @@ class BenchmarkCNN:
         log_fn(f"Model:       {self.model_name}")
         log_fn(f"Dataset:     imagenet ({'TFRecords ' + p.data_dir if p.data_dir else 'synthetic'})")
         log_fn(f"Mode:        {'evaluation' if p.eval else 'forward-only' if p.forward_only else 'training'}")
+        if p.data_dir and not p.eval and not p.forward_only:
+            log_fn("Distortions: " + (f"crop+flip{'+color' if p.color_distortions else ''}, resize={p.resize_method}"
+                                      if p.distortions else "none (central crop), resize=bilinear"))
         log_fn(f"SingleSess:  False")
         log_fn(f"Batch size:  {self.batch_size * self.size} global")
         log_fn(f"             {self.batch_size} per device")
@@ -237,7 +240,8 @@ class BenchmarkCNN:
         return ImageNetLoader(p.data_dir, self.batch_size, self.model.image_size, self.model.image_channels,
                               self.device, rank=self.rank, world=self.size, train=train, loop=loop,
                               seed=p.tf_random_seed, reader_threads=p.datasets_num_private_threads or 4,
-                              decode_threads=p.num_decode_threads or 8)
+                              decode_threads=p.num_decode_threads or 8, distort=p.distortions,
+                              color=p.color_distortions, resize_method=p.resize_method)
 
     def _sum_over_ranks(self, counts):
         """(examples, top-1 hits, top-5 hits) summed over the workers."""

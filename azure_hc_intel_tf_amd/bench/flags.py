@@ -79,6 +79,12 @@ FLAGS: List[Flag] = [
     Flag("data_name", None, str, "dataset name (imagenet)"),
     Flag("datasets_num_private_threads", None, int, "TFRecord reader threads per worker (real data)"),
     Flag("num_decode_threads", None, int, "JPEG decode threads per worker (real data)"),
+    Flag("distortions", True, parse_bool, "real-data training preprocessing: true = random distorted crop + flip "
+         "(+ colour with --color_distortions); false = the eval preprocessing (87.5 % central crop, no flip, no "
+         "colour, bilinear) on the shuffled train data"),
+    Flag("resize_method", "bilinear", str, "resize of the training crop to the model's input size; round_robin = "
+         "batch position % 4 over nearest, bilinear, bicubic, area",
+         choices=["round_robin", "nearest", "bilinear", "bicubic", "area"]),
     # --- tf_cnn_benchmarks flags used by the BASELINE configs / common runs
     Flag("num_gpus", 1, int, "GPUs per process (horovod: 1)"),
     Flag("use_fp16", False, parse_bool, "16-bit compute with loss scaling on the HIP kernels: IEEE fp16 "
@@ -123,6 +129,9 @@ FLAGS: List[Flag] = [
          choices=["native", "torch"]),
     Flag("gradient_compression", "none", str, "none | fp16 | bf16 (Horovod Compression)",
          choices=["none", "fp16", "bf16"]),
+    Flag("color_distortions", False, parse_bool, "with --distortions: also tf_cnn_benchmarks' distort_color (random "
+         "brightness, saturation, hue, contrast; the preprocess_distort HIP kernels). Upstream's --distortions=true "
+         "is --distortions=true --color_distortions=true here"),
     Flag("json_summary", None, str, "write the run summary JSON to this path"),
     Flag("comm_profile", True, parse_bool, "after the timed run (N>1, GPU): measure allreduce time, exposed "
          "communication and overlap % for the JSON summary"),

@@ -13,7 +13,9 @@ per MI355X:
   -> pinned staging slot                    crops packed back to back
   -> one H2D copy + HIP preprocess kernel   bilinear resize, flip, x/127.5 - 1, NHWC bf16
                                             written IN PLACE into the static input buffer
-                                            the captured HIP graph reads
+                                            the captured HIP graph reads; with colour
+                                            distortion or another resize method the
+                                            ``preprocess_distort`` kernels instead (below)
 
 A background thread keeps ``depth`` batches in flight, so host decode overlaps the GPU step;
 with fewer CPU cores than the GPU can consume, the run is input-bound and the log says so
@@ -21,6 +23,22 @@ with fewer CPU cores than the GPU can consume, the run is input-bound and the lo
 Eval mode (``train=False``) uses the 87.5 % central crop without flips; ``loop=False`` reads the
 split exactly once (``--eval``), padding the short last batch with label -1 rows.
 Normalisation x/127.5 - 1 is this engine's convention (parity with the TF build unpinned).
+
+Distortions (tf_cnn_benchmarks' ``--distortions`` / ``--resize_method``; the loader's ``distort``,
+``color`` and ``resize_method`` arguments). ``distort=False`` trains on the eval crop: shuffled train
+shards, 87.5 % central crop, no flip, no colour, bilinear. ``color=True`` adds upstream's
+``distort_color`` after the resize: brightness x + db, saturation (s <- clamp(s * fs, 0, 1) in HSV),
+hue (h <- frac(h + dh)) and contrast ((x - m) * fc + m, m the per-channel mean of the image at that
+point), on x = v / 255, as brightness-saturation-hue-contrast at even batch positions and
+brightness-contrast-saturation-hue at odd ones, then clamp to [0, 1]. The producer thread, the only
+one that draws, takes db ~ U(-32/255, 32/255), fs ~ U(0.5, 1.5), dh ~ U(-0.2, 0.2), fc ~ U(0.5, 1.5)
+from a numpy Generator seeded with (seed, rank), so a seed reproduces a run. ``resize_method`` is
+nearest | bilinear | bicubic | area, or round_robin = batch position % 4 in that order (upstream also
+rotates it with the global step; not reproduced). bicubic is Keys cubic convolution (a = -0.75) with
+weights from the exact fraction, not TF's 1024-entry weight table (parity unpinned). The defaults
+(crop + flip, no colour, bilinear) keep the ``preprocess_images`` kernel; anything else runs
+``preprocess_distort`` (csrc/kernels/distort.hip) on the GPU and ``preprocess_distort_reference``,
+the definition of both, on ``--device=cpu``.
 """
 from __future__ import annotations
 
@@ -102,6 +120,149 @@ def preprocess_reference(crops: List[np.ndarray], flips: List[int], out: torch.T
     return out
 
 
+RESIZE_METHODS = ("nearest", "bilinear", "bicubic", "area")  # method codes 0..3; round_robin cycles them
+
+
+def distort_work_numel(batch: int, size: int) -> int:
+    """float32 elements of scratch ``preprocess_distort`` needs: the per-block partial sums of the
+    contrast mean, 4 per 256-pixel block of every image."""
+    return batch * ((size * size + 255) // 256) * 4
+
+
+def _keys_weights(t: torch.Tensor):
+    """Keys cubic-convolution weights (a = -0.75) of the taps at -1, 0, 1, 2 for the fraction t."""
+    a = -0.75
+    x0, x1, x2, x3 = t + 1, t, 1 - t, 2 - t
+    return [((a * x0 - 5 * a) * x0 + 8 * a) * x0 - 4 * a, ((a + 2) * x1 - (a + 3)) * x1 * x1 + 1,
+            ((a + 2) * x2 - (a + 3)) * x2 * x2 + 1, ((a * x3 - 5 * a) * x3 + 8 * a) * x3 - 4 * a]
+
+
+def resize_reference(img: torch.Tensor, S: int, flip: int, method: int) -> torch.Tensor:
+    """``img`` [h, w, 3] (float32 or float64, values 0..255) -> [S, S, 3] in the same dtype: TF1
+    resizing, source coordinate dst * in / out, the flip applied to the output x."""
+    dt = img.dtype
+    h, w = img.shape[:2]
+    yo = torch.arange(S)
+    xo = S - 1 - torch.arange(S) if flip else torch.arange(S)
+    if method == 1:  # preprocess_reference's bilinear, operation for operation
+        ys = yo.to(dt) * (h / float(S))
+        xs = xo.to(dt) * (w / float(S))
+        y0 = ys.long().clamp(max=h - 1)
+        x0 = xs.long().clamp(max=w - 1)
+        y1 = (y0 + 1).clamp(max=h - 1)
+        x1 = (x0 + 1).clamp(max=w - 1)
+        ly = (ys - y0.to(dt)).view(S, 1, 1)
+        lx = (xs - x0.to(dt)).view(1, S, 1)
+        a = img[y0][:, x0]
+        b = img[y0][:, x1]
+        cc = img[y1][:, x0]
+        d = img[y1][:, x1]
+        top = a + (b - a) * lx
+        bot = cc + (d - cc) * lx
+        return top + (bot - top) * ly
+    if method == 0:  # index (dst * in) / out in integers
+        return img[(yo * h) // S][:, (xo * w) // S]
+    if method == 2:  # Keys bicubic, taps clamped to the edge, weights from the exact fraction
+        iy, ix = (yo * h) // S, (xo * w) // S
+        wy = _keys_weights((yo * h - iy * S).to(dt) / S)
+        wx = _keys_weights((xo * w - ix * S).to(dt) / S)
+        v = torch.zeros(S, S, 3, dtype=dt)
+        for i in range(4):
+            rows = img[(iy + i - 1).clamp(0, h - 1)]
+            row = torch.zeros(S, S, 3, dtype=dt)
+            for j in range(4):
+                row = row + wx[j].view(1, S, 1) * rows[:, (ix + j - 1).clamp(0, w - 1)]
+            v = v + wy[i].view(S, 1, 1) * row
+        return v
+    if method == 3:  # area: overlap of [i*in/out, (i+1)*in/out) with each source pixel, in 1/out units
+        def overlap(dst, n):
+            lo = (dst * n).view(S, 1)
+            j = torch.arange(n).view(1, n)
+            return (torch.minimum((j + 1) * S, lo + n) - torch.maximum(j * S, lo)).clamp(min=0).to(dt)
+
+        return torch.einsum("yh,hwc,xw->yxc", overlap(yo, h), img, overlap(xo, w)) / float(h * w)
+    raise ValueError(f"resize method {method}: 0 nearest | 1 bilinear | 2 bicubic | 3 area")
+
+
+def _rgb_to_hcv(x: torch.Tensor):
+    """RGB -> (hue in [0, 1], chroma = max - min = s * v, value = max): HSV with the saturation
+    kept multiplied by the value, so nothing divides by a maximum that may be <= 0."""
+    r, g, b = x.unbind(-1)
+    mx, mn = x.max(-1).values, x.min(-1).values
+    d = mx - mn
+    ds = torch.where(d > 0, d, torch.ones_like(d))
+    h6 = torch.where(r == mx, (g - b) / ds, torch.where(g == mx, 2 + (b - r) / ds, 4 + (r - g) / ds))
+    h = torch.where(d > 0, h6, torch.zeros_like(d)) / 6
+    return h - torch.floor(h), d, mx
+
+
+def _hcv_to_rgb(h: torch.Tensor, c: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    h6 = h * 6
+    fl = torch.floor(h6)
+    f = h6 - fl
+    i = (fl.long() % 6).unsqueeze(-1)
+    p, q, t = v - c, v - c * f, v - c * (1 - f)
+    r = torch.stack([v, q, p, p, t, v], -1).gather(-1, i)
+    g = torch.stack([t, v, v, q, p, p], -1).gather(-1, i)
+    b = torch.stack([p, p, t, v, v, q], -1).gather(-1, i)
+    return torch.cat([r, g, b], -1)
+
+
+def adjust_saturation(x: torch.Tensor, fs: float) -> torch.Tensor:
+    """RGB -> HSV, s <- clamp(s * fs, 0, 1), HSV -> RGB (a pixel whose maximum is <= 0 turns grey)."""
+    h, c, v = _rgb_to_hcv(x)
+    return _hcv_to_rgb(h, torch.minimum(c * fs, v.clamp(min=0)), v)
+
+
+def adjust_hue(x: torch.Tensor, dh: float) -> torch.Tensor:
+    """RGB -> HSV, h <- frac(h + dh), HSV -> RGB."""
+    h, c, v = _rgb_to_hcv(x)
+    h = h + dh
+    return _hcv_to_rgb(h - torch.floor(h), c, v)
+
+
+def distort_color_reference(x: torch.Tensor, db: float, fs: float, dh: float, fc: float,
+                            ordering: int) -> torch.Tensor:
+    """The colour stage on one image x [S, S, 3] in 0..1 units (not yet clamped on entry)."""
+    def contrast(x):
+        m = x.mean(dim=(0, 1), keepdim=True)
+        return (x - m) * fc + m
+
+    x = x + db
+    if ordering == 0:
+        x = contrast(adjust_hue(adjust_saturation(x, fs), dh))
+    elif ordering == 1:
+        x = adjust_hue(adjust_saturation(contrast(x), fs), dh)
+    else:
+        raise ValueError(f"colour ordering {ordering}: 0 or 1 (-1: no colour stage)")
+    return x.clamp(0, 1)
+
+
+def preprocess_distort_reference(crops: List[np.ndarray], flips: List[int], params, out: torch.Tensor,
+                                 scale=SCALE, bias=BIAS, dtype=torch.float32) -> torch.Tensor:
+    """Definition of the ``preprocess_distort`` HIP kernels and the CPU path of the distortions.
+    ``params`` [B][8] float32: brightness delta, saturation factor, hue delta, contrast factor,
+    colour ordering (0 | 1, -1 = no colour stage), resize method (0 nearest | 1 bilinear | 2 bicubic |
+    3 area), 0, 0. Per image: resize the crop to S x S (``resize_reference``), the colour stage on
+    v / 255 (``distort_color_reference``), v * scale + bias with scale and bias as float32 values,
+    NHWC with zero pad channels. Arithmetic in ``dtype`` (float64: the tests' reference)."""
+    S = out.shape[1]
+    out.zero_()
+    params = np.asarray(params, dtype=np.float32).reshape(-1, 8)
+    sc = torch.tensor(scale, dtype=torch.float32).to(dtype)
+    bi = torch.tensor(bias, dtype=torch.float32).to(dtype)
+    for i, (c, fl) in enumerate(zip(crops, flips)):
+        db, fs, dh, fc = (float(p) for p in params[i, :4])
+        ordering, method = int(params[i, 4]), int(params[i, 5])
+        if not (np.isfinite(params[i]).all() and fs >= 0 and fc >= 0 and params[i, 6] == 0 and params[i, 7] == 0):
+            raise ValueError(f"distortion parameters of image {i}: {params[i].tolist()}")
+        v = resize_reference(torch.from_numpy(np.array(c, dtype=np.uint8)).to(dtype), S, int(fl), method)
+        if ordering != -1:
+            v = 255 * distort_color_reference(v / 255, db, fs, dh, fc, ordering)
+        out[i, :, :, :3] = (v * sc + bi).to(out.dtype)
+    return out
+
+
 _END = object()  # producer -> consumer: a loop=False pass is exhausted
 
 
@@ -111,8 +272,17 @@ class ImageNetLoader:
     def __init__(self, data_dir: str, batch_size: int, image_size: int, channels: int, device,
                  rank: int = 0, world: int = 1, train: bool = True, seed: int = 0, reader_threads: int = 4,
                  decode_threads: int = 8, depth: int = 3, shuffle_buffer: int = 4096, subset: Optional[str] = None,
-                 loop: bool = True):
+                 loop: bool = True, distort: bool = True, color: bool = False, resize_method: str = "bilinear"):
         self.B = batch_size
+        # distort / color / resize_method: see the module docstring; evaluation loaders ignore them
+        if resize_method != "round_robin" and resize_method not in RESIZE_METHODS:
+            raise ValueError(f"resize_method {resize_method!r}: round_robin | " + " | ".join(RESIZE_METHODS))
+        self.distort = bool(distort) or not train
+        self.color = bool(color) and train and self.distort
+        self.resize_method = resize_method if train and self.distort else "bilinear"
+        # the defaults keep the preprocess_images kernel / preprocess_reference
+        self.distort_op = self.color or self.resize_method != "bilinear"
+        self._rng = np.random.default_rng([seed, rank])
         # loop=False: ONE pass over this rank's share of the split (evaluation): a short last batch
         # is padded (label -1, an already-decoded image repeated) and next_into returns the number
         # of real rows, 0 once the data is exhausted
@@ -134,13 +304,17 @@ class ImageNetLoader:
         self.max_side = 4 * image_size
         self.pf = native().Prefetcher(self.files, rank=rank, world=world, threads=reader_threads,
                                       shuffle_buffer=shuffle_buffer if train else 1, capacity=max(8192, shuffle_buffer),
-                                      seed=seed, train=train, loop=loop)
+                                      seed=seed, train=train, loop=loop, distort=self.distort)
         self.pool = ThreadPoolExecutor(max_workers=decode_threads, thread_name_prefix="hcb-decode")
         cap = batch_size * self.max_side * self.max_side * 3
         pin = self.device.type == "cuda"
         self.slots = [torch.empty(cap, dtype=torch.uint8, pin_memory=pin) for _ in range(depth)]
         self.dev_stage = torch.empty(cap, dtype=torch.uint8, device=self.device) if pin else None
         self.dev_desc = torch.empty((batch_size, 4), dtype=torch.int64, device=self.device) if pin else None
+        if pin and self.distort_op:
+            self.dev_params = torch.empty((batch_size, 8), dtype=torch.float32, device=self.device)
+            self.dev_work = torch.empty(distort_work_numel(batch_size, image_size), dtype=torch.float32,
+                                        device=self.device)
         self.free: "queue.Queue" = queue.Queue()
         for i in range(depth):
             self.free.put((i, None))
@@ -153,6 +327,22 @@ class ImageNetLoader:
         self._thr.start()
 
     # ---------------------------------------------------------------- producer thread
+    def _draw_params(self) -> np.ndarray:
+        """[B][8] rows for preprocess_distort: one draw per image and batch, in batch order."""
+        B = self.B
+        prm = np.zeros((B, 8), dtype=np.float32)
+        prm[:, 1] = prm[:, 3] = 1.0
+        prm[:, 4] = -1.0
+        pos = np.arange(B)
+        prm[:, 5] = pos % 4 if self.resize_method == "round_robin" else RESIZE_METHODS.index(self.resize_method)
+        if self.color:
+            prm[:, 0] = self._rng.uniform(-32.0 / 255.0, 32.0 / 255.0, B)
+            prm[:, 1] = self._rng.uniform(0.5, 1.5, B)
+            prm[:, 2] = self._rng.uniform(-0.2, 0.2, B)
+            prm[:, 3] = self._rng.uniform(0.5, 1.5, B)
+            prm[:, 4] = pos % 2
+        return prm
+
     def _produce(self):
         import time
 
@@ -186,8 +376,9 @@ class ImageNetLoader:
                 crops += [crops[0]] * (self.B - real)
                 labels = np.full(self.B, -1, dtype=np.int64)
                 labels[:real] = [s[1] for s in samples]
+                prm = self._draw_params() if self.distort_op else None
                 self.decode_s += time.perf_counter() - t0
-                self.ready.put((slot, desc, labels, crops if self.device.type != "cuda" else None, real))
+                self.ready.put((slot, desc, labels, crops if self.device.type != "cuda" else None, real, prm))
         except Exception as e:  # surfaced on the consumer side
             self._err = e
             self.ready.put(None)
@@ -206,7 +397,7 @@ class ImageNetLoader:
         if item is _END:
             self._exhausted = True
             return 0
-        slot, desc, lab, crops, real = item
+        slot, desc, lab, crops, real, prm = item
         if self.device.type == "cuda":
             nbytes = int(desc[real - 1, 0] + desc[real - 1, 1] * desc[real - 1, 2] * 3)
             self.dev_stage[:nbytes].copy_(self.slots[slot][:nbytes], non_blocking=True)
@@ -215,12 +406,21 @@ class ImageNetLoader:
             labels.copy_(torch.from_numpy(lab), non_blocking=True)
             from ..ops import _ext
 
-            _ext.ops().preprocess_images(self.dev_stage, self.dev_desc, desc_t, images, list(SCALE), list(BIAS))
+            if prm is None:
+                _ext.ops().preprocess_images(self.dev_stage, self.dev_desc, desc_t, images, list(SCALE), list(BIAS))
+            else:
+                prm_t = torch.from_numpy(prm)
+                self.dev_params.copy_(prm_t, non_blocking=True)
+                _ext.ops().preprocess_distort(self.dev_stage, self.dev_desc, desc_t, self.dev_params, prm_t, images,
+                                              self.dev_work, list(SCALE), list(BIAS))
             ev = torch.cuda.Event()
             ev.record()
             self.free.put((slot, ev))
         else:
-            preprocess_reference(crops, [int(d[3]) for d in desc], images)
+            if prm is None:
+                preprocess_reference(crops, [int(d[3]) for d in desc], images)
+            else:
+                preprocess_distort_reference(crops, [int(d[3]) for d in desc], prm, images)
             labels.copy_(torch.from_numpy(lab))
             self.free.put((slot, None))
         self.batches += 1

@@ -7,6 +7,7 @@
 // host BEFORE anything reaches the GPU (an out-of-range gather must never be launched)
 // and enqueues on the current HIP stream.
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include <torch/library.h>
@@ -1062,6 +1063,73 @@ void preprocess_images(const Tensor& src, const Tensor& desc, const Tensor& desc
                                 (int)out.size(1), (int)out.size(3), sc, bi, f32, cur_stream());
 }
 
+// preprocess_images with a colour stage and a resize method per image (kernels/distort.hip). params
+// [B][8] float32 = brightness delta, saturation factor, hue delta, contrast factor, ordering (-1 | 0 | 1),
+// method (0..3), 0, 0; desc_host / params_host: the CPU copies, checked here before anything is launched.
+// work: at least B * ceil(S*S / 256) * 4 float32 of scratch, no need to clear it
+void preprocess_distort(const Tensor& src, const Tensor& desc, const Tensor& desc_host, const Tensor& params,
+                        const Tensor& params_host, const Tensor& out, const Tensor& work, at::ArrayRef<double> scale,
+                        at::ArrayRef<double> bias) {
+  check_cuda(src, "src");
+  check_cuda(desc, "desc");
+  check_cuda(params, "params");
+  check_cuda(work, "work");
+  const bool f32 = check_act_or_f32(out, "out");
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.is_contiguous(), "hcb.preprocess_distort: src uint8 contiguous");
+  TORCH_CHECK(desc.scalar_type() == at::kLong && desc.dim() == 2 && desc.size(1) == 4 && desc.is_contiguous(),
+              "hcb.preprocess_distort: desc int64 [B][4]");
+  TORCH_CHECK(!desc_host.is_cuda() && desc_host.scalar_type() == at::kLong && desc_host.is_contiguous() &&
+                  desc_host.sizes() == desc.sizes(),
+              "hcb.preprocess_distort: desc_host must be the CPU copy of desc");
+  const int64_t B = desc.size(0);
+  TORCH_CHECK(params.scalar_type() == at::kFloat && params.dim() == 2 && params.size(0) == B && params.size(1) == 8 &&
+                  params.is_contiguous(),
+              "hcb.preprocess_distort: params float32 [B][8]");
+  TORCH_CHECK(!params_host.is_cuda() && params_host.scalar_type() == at::kFloat && params_host.is_contiguous() &&
+                  params_host.sizes() == params.sizes(),
+              "hcb.preprocess_distort: params_host must be the CPU copy of params");
+  TORCH_CHECK(out.dim() == 4 && out.is_contiguous() && out.size(1) == out.size(2) && out.size(3) % 8 == 0 &&
+                  out.size(3) >= 8,
+              "hcb.preprocess_distort: out [B][S][S][Cpad] contiguous, Cpad % 8 == 0");
+  TORCH_CHECK(scale.size() == 3 && bias.size() == 3, "hcb.preprocess_distort: 3 scales / biases");
+  TORCH_CHECK(B <= out.size(0), "hcb.preprocess_distort: more crops than output images");
+  const int64_t S = out.size(1);
+  TORCH_CHECK(S * S < (1ll << 31), "hcb.preprocess_distort: image too large");
+  const int64_t* d = desc_host.data_ptr<int64_t>();
+  const float* q = params_host.data_ptr<float>();
+  bool any_colour = false;
+  for (int64_t i = 0; i < B; ++i) {
+    TORCH_CHECK(d[4 * i] >= 0 && d[4 * i + 1] > 0 && d[4 * i + 2] > 0 &&
+                    d[4 * i] + d[4 * i + 1] * d[4 * i + 2] * 3 <= src.numel(),
+                "hcb.preprocess_distort: crop ", i, " outside the staging buffer");
+    // the nearest / bicubic / area index arithmetic forms (dst + 1) * in in 32 bits
+    TORCH_CHECK(d[4 * i + 1] * S < (1ll << 31) && d[4 * i + 2] * S < (1ll << 31),
+                "hcb.preprocess_distort: crop ", i, " too large");
+    const float* r = q + 8 * i;
+    for (int k = 0; k < 8; ++k)
+      TORCH_CHECK(std::isfinite(r[k]), "hcb.preprocess_distort: parameter ", k, " of image ", i, " is not finite");
+    TORCH_CHECK(r[5] == 0.f || r[5] == 1.f || r[5] == 2.f || r[5] == 3.f, "hcb.preprocess_distort: resize method of image ",
+                i, " must be 0 (nearest), 1 (bilinear), 2 (bicubic) or 3 (area)");
+    TORCH_CHECK(r[4] == -1.f || r[4] == 0.f || r[4] == 1.f, "hcb.preprocess_distort: colour ordering of image ", i,
+                " must be -1 (none), 0 or 1");
+    TORCH_CHECK(r[1] >= 0.f && r[3] >= 0.f, "hcb.preprocess_distort: saturation and contrast factors of image ", i,
+                " must be >= 0");
+    TORCH_CHECK(r[6] == 0.f && r[7] == 0.f, "hcb.preprocess_distort: the spare parameter slots of image ", i,
+                " must be 0");
+    any_colour |= r[4] >= 0.f;
+  }
+  TORCH_CHECK(work.scalar_type() == at::kFloat && work.is_contiguous() &&
+                  work.numel() >= hcb::preprocess_distort_work_floats((int)B, (int)S),
+              "hcb.preprocess_distort: work too small: float32, at least B * ceil(S*S / 256) * 4 = ",
+              hcb::preprocess_distort_work_floats((int)B, (int)S), " elements");
+  const float sc[3] = {(float)scale[0], (float)scale[1], (float)scale[2]};
+  const float bi[3] = {(float)bias[0], (float)bias[1], (float)bias[2]};
+  if (B == 0) return;
+  hcb::launch_preprocess_distort(src.data_ptr<uint8_t>(), desc.data_ptr<int64_t>(), params.data_ptr<float>(),
+                                 any_colour, (int)B, out.data_ptr(), work.data_ptr<float>(), (int)S, (int)out.size(3), sc,
+                                 bi, f32, cur_stream());
+}
+
 static int pack_mode(const Tensor& t, const char* what) {
   switch (t.scalar_type()) {
     case at::kFloat: return 0;
@@ -1327,6 +1395,8 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("bn_bwd_apply_acc(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, Tensor(a!) dx, int lddx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor acc, int R, Tensor(b!) dgamma, Tensor(c!) dbeta, int relu, Tensor(d!)? shift_out=None, Tensor? pool_amax=None, int[]? pool_geom=None, Tensor? add=None, int ldadd=0) -> ()");
   m.def("bn_stats_acc(Tensor x, int ldx, int M, int C, Tensor(a!) acc, int R, Tensor? shift=None) -> ()");
   m.def("preprocess_images(Tensor src, Tensor desc, Tensor desc_host, Tensor(a!) out, float[] scale, float[] bias) -> ()");
+  m.def("preprocess_distort(Tensor src, Tensor desc, Tensor desc_host, Tensor params, Tensor params_host, "
+        "Tensor(a!) out, Tensor(b!) work, float[] scale, float[] bias) -> ()");
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
         "Tensor(e!) run_mean, Tensor(f!) run_var, Tensor? shift=None) -> ()");
@@ -1384,6 +1454,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("bn_relu_maxpool_acc", bn_relu_maxpool_acc);
   m.impl("dropout_bwd", dropout_bwd);
   m.impl("preprocess_images", preprocess_images);
+  m.impl("preprocess_distort", preprocess_distort);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);

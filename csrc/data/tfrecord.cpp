@@ -441,6 +441,7 @@ struct PrefetchConfig {
   int capacity = 8192;
   uint64_t seed = 0;
   bool train = true;
+  bool distort = true;  // train only; false: the eval crop (central, no flip) on shuffled train data
   bool loop = true;
   bool verify_crc = true;
   float min_object_covered = 0.1f, ar_lo = 0.75f, ar_hi = 1.33f, area_lo = 0.05f, area_hi = 1.0f;
@@ -511,7 +512,7 @@ class Prefetcher {
 
  private:
   void finish(Sample& s) {
-    if (cfg_.train) {
+    if (cfg_.train && cfg_.distort) {
       s.win = distorted_crop(s.h, s.w, s.boxes, cfg_.min_object_covered, cfg_.ar_lo, cfg_.ar_hi, cfg_.area_lo,
                              cfg_.area_hi, cfg_.attempts, crop_rng_);
       s.flip = (int)(crop_rng_() & 1);
@@ -716,7 +717,8 @@ PYBIND11_MODULE(_hcb_data, m) {
 
   py::class_<Prefetcher>(m, "Prefetcher")
       .def(py::init([](std::vector<std::string> files, int rank, int world, int threads, int shuffle_buffer, int capacity,
-                       uint64_t seed, bool train, bool loop, bool verify_crc, int label_offset, float central_fraction) {
+                       uint64_t seed, bool train, bool loop, bool verify_crc, int label_offset, float central_fraction,
+                       bool distort) {
              PrefetchConfig c;
              c.files = std::move(files);
              c.rank = rank;
@@ -730,12 +732,13 @@ PYBIND11_MODULE(_hcb_data, m) {
              c.verify_crc = verify_crc;
              c.label_offset = label_offset;
              c.central_fraction = central_fraction;
+             c.distort = distort;
              return new Prefetcher(std::move(c));
            }),
            py::arg("files"), py::arg("rank") = 0, py::arg("world") = 1, py::arg("threads") = 4,
            py::arg("shuffle_buffer") = 2048, py::arg("capacity") = 8192, py::arg("seed") = 0, py::arg("train") = true,
            py::arg("loop") = true, py::arg("verify_crc") = true, py::arg("label_offset") = 0,
-           py::arg("central_fraction") = 0.875f)
+           py::arg("central_fraction") = 0.875f, py::arg("distort") = true)
       .def("next",
            [](Prefetcher& p, int n) {
              std::vector<Sample> v;

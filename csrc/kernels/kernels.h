@@ -269,6 +269,15 @@ void launch_synth_labels(int64_t* out, int n, int ncls, uint64_t seed, hipStream
 // to S x S, optional horizontal flip, x*scale[c]+bias[c], NHWC bf16 with Cpad channels
 void launch_preprocess_images(const uint8_t* src, const int64_t* desc, int B, void* out, int S, int Cpad,
                               const float* scale, const float* bias, bool f32, hipStream_t st);
+// the same with tf_cnn_benchmarks' colour distortion and resize methods (distort.hip): params [B][8] =
+// brightness delta, saturation factor, hue delta, contrast factor, ordering (-1 none | 0 | 1), method
+// (0 nearest | 1 bilinear | 2 bicubic | 3 area), 0, 0. work: preprocess_distort_work_floats(B, S) floats
+// of scratch for the per-block partial sums of the contrast mean (4 per 256-pixel block), written
+// before they are read; any_colour = false (no row has a colour stage) skips the launch that fills it
+int64_t preprocess_distort_work_floats(int B, int S);
+void launch_preprocess_distort(const uint8_t* src, const int64_t* desc, const float* params, bool any_colour, int B,
+                               void* out, float* work, int S, int Cpad, const float* scale, const float* bias,
+                               bool f32, hipStream_t st);
 
 // ---------------------------------------------------------------- space-to-depth stem (stem.hip)
 void launch_stem_s2d_f32(const float* x, int N, int H, int W, int ldx, uint16_t* out, int64_t plane, int Hs, int Ws,
