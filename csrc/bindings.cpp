@@ -1156,6 +1156,43 @@ void bucket_unpack(const Tensor& src, const Tensor& dst, double scale) {
                             pack_mode(src, "bucket_unpack"), cur_stream());
 }
 
+// ---- tensor fusion of the hvd API: scattered tensors <-> the flat fp32 fusion buffer, one launch.
+// The table lives on the device, so its CONTENT cannot be checked here without a read-back: the
+// host mirror it is uploaded from is validated where the layout is built and where rows are bound
+// (parallel/fusion.py, FusionBuffer._validate: off + n within flat, off % 4 == 0, tag 0..2, slots
+// disjoint, pointer aligned to the element size). Checked here: the table's shape / dtype / device
+// and the flat buffer. A slice of rows (one bucket) is a valid table: prefixes are relative to row 0.
+static int fusion_check(const Tensor& table, const Tensor& flat, const char* what) {
+  check_cuda(table, "table");
+  check_f32(flat, "flat");
+  constexpr int64_t K = (int64_t)(sizeof(hcb::FusionEntry) / sizeof(int64_t));
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == K && table.is_contiguous(),
+              "hcb.", what, ": table must be a contiguous int64 [n][", K, "] tensor");
+  TORCH_CHECK(flat.is_contiguous() && flat.device() == table.device(), "hcb.", what,
+              ": flat must be contiguous and on the table's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(flat.data_ptr()) % 16 == 0, "hcb.", what, ": flat must be 16-byte aligned");
+  TORCH_CHECK(table.size(0) < (1ll << 31), "hcb.", what, ": too many entries");
+  return (int)table.size(0);
+}
+// every entry adds at most one partial chunk to numel / FUSION_CHUNK
+static int64_t fusion_max_chunks(const Tensor& table, const Tensor& flat) {
+  return flat.numel() / hcb::FUSION_CHUNK + table.size(0);
+}
+
+void fusion_pack(const Tensor& table, const Tensor& flat, double scale) {
+  const int n = fusion_check(table, flat, "fusion_pack");
+  hcb::launch_fusion_pack(reinterpret_cast<const hcb::FusionEntry*>(table.data_ptr<int64_t>()), n, flat.data_ptr<float>(),
+                          fusion_max_chunks(table, flat), (float)scale, cur_stream());
+}
+
+void fusion_unpack(const Tensor& table, const Tensor& flat, double scale) {
+  const int n = fusion_check(table, flat, "fusion_unpack");
+  hcb::launch_fusion_unpack(reinterpret_cast<const hcb::FusionEntry*>(table.data_ptr<int64_t>()), n,
+                            flat.data_ptr<float>(), fusion_max_chunks(table, flat), (float)scale, cur_stream());
+}
+
+int64_t fusion_chunk() { return hcb::fusion_chunk_elems(); }
+
 // ---------------------------------------------------------------- space-to-depth stem
 void stem_s2d(const Tensor& x, const Tensor& out, int64_t pad) {
   check_cuda(x, "x");
@@ -1406,6 +1443,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("synth_labels(Tensor(a!) out, int ncls, int seed) -> ()");
   m.def("bucket_pack(Tensor src, Tensor(a!) dst, float scale) -> ()");
   m.def("bucket_unpack(Tensor src, Tensor(a!) dst, float scale) -> ()");
+  m.def("fusion_pack(Tensor table, Tensor(a!) flat, float scale) -> ()");
+  m.def("fusion_unpack(Tensor table, Tensor flat, float scale) -> ()");
+  m.def("fusion_chunk() -> int", fusion_chunk);
   m.def("stem_s2d(Tensor x, Tensor(a!) out, int pad) -> ()");
   m.def("set_deterministic(bool on) -> ()", set_deterministic);
   m.def("stem_wfold(Tensor w, Tensor(a!) wp) -> ()");
@@ -1458,6 +1498,8 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);
+  m.impl("fusion_pack", fusion_pack);
+  m.impl("fusion_unpack", fusion_unpack);
   m.impl("stem_s2d", stem_s2d);
   m.impl("stem_wfold", stem_wfold);
   m.impl("stem_wgrad_unfold", stem_wgrad_unfold);

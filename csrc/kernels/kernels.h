@@ -296,6 +296,22 @@ void launch_bucket_pack(const float* src, void* dst, int64_t n, float scale, int
                         hipStream_t st);
 void launch_bucket_unpack(const void* src, float* dst, int64_t n, float scale, int mode,
                           hipStream_t st);
+// Tensor fusion of the hvd API (fusion.hip): any number of scattered tensors <-> one flat fp32
+// buffer in ONE launch. pack: flat[off + j] = float(src[j]) * scale; unpack: dst[j] =
+// T(flat[off + j] * scale). max_chunks: an upper bound of the table's chunk count (sizes the grid).
+constexpr int FUSION_CHUNK = 4096;  // elements of one tensor handled by one block at a time
+struct FusionEntry {  // all int64 so the table is a plain int64 tensor [n][5]
+  int64_t ptr;     // the tensor's data pointer
+  int64_t off;     // its slot in the flat buffer (elements, a multiple of 4)
+  int64_t n;       // elements (0 is legal)
+  int64_t tag;     // 0 fp32, 1 bf16, 2 IEEE fp16
+  int64_t chunk0;  // exclusive prefix of ceil(n / FUSION_CHUNK) over the rows
+};
+int fusion_chunk_elems();
+void launch_fusion_pack(const FusionEntry* entries_dev, int n_entries, float* flat, int64_t max_chunks, float scale,
+                        hipStream_t st);
+void launch_fusion_unpack(const FusionEntry* entries_dev, int n_entries, const float* flat, int64_t max_chunks,
+                          float scale, hipStream_t st);
 // debug: one wave sleeps ~ms milliseconds (bounded, s_memrealtime-timed) on stream st
 void launch_debug_sleep(int ms, hipStream_t st);
 
