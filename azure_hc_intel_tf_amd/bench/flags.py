@@ -46,7 +46,7 @@ FLAGS: List[Flag] = [
     Flag("num_warmup_batches", None, int, "untimed warmup steps (default: model/device dependent)"),
     Flag("num_batches", None, int, "timed steps (default 100; with --eval on real data and neither this nor "
          "--num_epochs given: one pass over the validation split)"),
-    Flag("model", "trivial", str, "model name: resnet50|101|152[_v1.5], inception3, vgg11|16|19, alexnet, googlenet, "
+    Flag("model", "trivial", str, "model name: resnet50|101|152[_v1.5], inception3, mobilenet, vgg11|16|19, alexnet, googlenet, "
          "overfeat, lenet, trivial"),
     Flag("num_intra_threads", 0, int, "host intra-op threads (CPU path: torch.set_num_threads)"),
     Flag("num_inter_threads", 0, int, "host inter-op threads (CPU path)"),
@@ -206,7 +206,7 @@ def noop_flags_set(p: Params) -> Dict[str, Any]:
 # (bf16x6 plane GEMMs, fp32 BN / pool / loss): their classes set F32_NATIVE_OK. Kept here, torch-free,
 # for the launcher's config echo; tests/test_cli.py checks it against the model classes.
 FP32_NATIVE_MODELS = frozenset({"resnet50", "resnet50_v1.5", "resnet101", "resnet101_v1.5", "resnet152",
-                                "resnet152_v1.5", "resnet50_v2", "resnet101_v2", "resnet152_v2", "inception3", "vgg11", "vgg16", "vgg19", "alexnet", "overfeat",
+                                "resnet152_v1.5", "resnet50_v2", "resnet101_v2", "resnet152_v2", "inception3", "mobilenet", "vgg11", "vgg16", "vgg19", "alexnet", "overfeat",
                                 "lenet", "googlenet", "trivial"})
 
 

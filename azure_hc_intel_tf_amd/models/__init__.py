@@ -25,6 +25,12 @@ def _inception3(**kw):
     return InceptionV3(**kw)
 
 
+def _mobilenet(**kw):
+    from .mobilenet import MobileNetV2
+
+    return MobileNetV2(**kw)
+
+
 def _trivial(**kw):
     from .trivial import Trivial
 
@@ -51,6 +57,7 @@ _MODELS = {
     "resnet101_v2": _resnet_v2(101),
     "resnet152_v2": _resnet_v2(152),
     "inception3": _inception3,
+    "mobilenet": _mobilenet,
     "trivial": _trivial,
     "vgg11": _seq("VGG", depth=11),
     "vgg16": _seq("VGG", depth=16),

@@ -133,6 +133,11 @@ class _BatchNorm(Layer):
     ``relu``, ``eps``, ``decay`` and ``out_shape``."""
 
     _acc = None  # (fwd acc, bwd acc, replicas) of the current step
+    relu6 = False  # the activation is ReLU6: min(max(v, 0), 6), backward mask 0 < v < 6 (relu_mode 3)
+
+    @property
+    def act_max(self):
+        return 6.0 if self.relu6 else None
 
     def _init_bn(self, ps: ParamStore, name: str, C: int, scale: bool = True):
         if scale:
@@ -172,14 +177,14 @@ class _BatchNorm(Layer):
         return self.gamma.data, self.beta.data, self.rmean.data, self.rvar.data
 
     def _bn_inference(self, z, y, residual=None):
-        return Fn.bn_inference(z, *self._bn_params(), self.eps, y, self.relu, residual=residual)
+        return Fn.bn_inference(z, *self._bn_params(), self.eps, y, self.relu, residual=residual, act_max=self.act_max)
 
     def _bn_forward_acc(self, z, y, residual=None, res_bn=None):
         """Finalize-free GPU BN of z from this step's forward accumulator (``_stat_bufs``)."""
         acc_f, _, R = self._acc
         return Fn.bn_forward_acc(z, *self._bn_params(), self.decay, self.eps, y, self.relu, acc_f, R,
                                  self.sv_mean.data, self.sv_invstd.data, residual=residual, shift=self._shift(),
-                                 res_bn=res_bn)
+                                 res_bn=res_bn, act_max=self.act_max)
 
     def _bn_backward_acc(self, dy, y, z, saved, relu_mode, dz, gres=None, **kw):
         """GPU BN backward through this step's backward accumulator; leaves the next step's shift."""
@@ -188,7 +193,8 @@ class _BatchNorm(Layer):
                                   self.beta.grad, dz, acc_b, R, gres, shift_out=self._shift(), **kw)
 
     def _bn_forward_ref(self, z, y, residual=None):
-        return Fn.bn_forward(z, *self._bn_params(), self.decay, self.eps, y, self.relu, residual=residual)
+        return Fn.bn_forward(z, *self._bn_params(), self.decay, self.eps, y, self.relu, residual=residual,
+                             act_max=self.act_max)
 
     def _bn_backward_ref(self, dy, y, z, saved, relu_mode, dz, gres=None):
         return Fn.bn_backward(dy, y, z, saved, self.gamma.data, self.beta.data, relu_mode, self.gamma.grad,
@@ -208,8 +214,11 @@ class ConvBN(_BatchNorm):
     def __init__(self, ps: ParamStore, name: str, in_shape, cout: int, kh: int, kw: int, sh: int = 1,
                  sw: int = 1, mode="SAME", relu: bool = True, bn: bool = True, need_dx: bool = True,
                  eps: float = 1e-5, decay: float = 0.9, logical_cin: Optional[int] = None,
-                 dilation: int = 1, scale: bool = True, init: str = "variance_scaling", bias: bool = True):
+                 dilation: int = 1, scale: bool = True, init: str = "variance_scaling", bias: bool = True,
+                 relu6: bool = False):
         H, W, cin = in_shape
+        assert not relu6 or (relu and bn), "ReLU6 is the BN pass's activation"
+        self.relu6 = relu6
         self.name = name
         self.in_shape = in_shape
         pt, pb, pl, pr = resolve_pads(mode, H, W, kh, kw, sh, sw, dilation, dilation)
@@ -269,7 +278,7 @@ class ConvBN(_BatchNorm):
         N = x.shape[0]
         P, Q, C = self.out_shape
         dev = x.device
-        if self.bn and not self.training and FUSE_INFER_BN:
+        if self.bn and not self.training and FUSE_INFER_BN and not self.relu6:  # (no clip in the GEMM epilogue)
             y = out if out is not None else empty_op((N, P, Q, C), dev)
             Fn.conv_bn_inference(x, self.spec, self.pack.pack if Fn.native(x) else None, self.w.data,
                                  *self._bn_params(), self.eps, y, self.relu, residual=residual)
@@ -367,8 +376,8 @@ class ConvBN(_BatchNorm):
     # ------------------------------------------------------------------ backward
     def bwd_fuse_request(self) -> Optional[Fn.BNBwdFuse]:
         """BN-backward reduction of this layer, to be fused into the GEMM producing its dy."""
-        if not (self.bn and FUSE_BN_BWD) or self._saved is None:
-            return None
+        if not (self.bn and FUSE_BN_BWD) or self._saved is None or self.relu6:
+            return None  # (ReLU6: the GEMM epilogues have no upper clip; bn_bwd_reduce_acc runs)
         x, z, y, saved, had_res = self._saved
         if z.dtype == torch.float32 and not (Fn.planes_mode() and z.is_cuda):
             return None  # fp32 fusion runs on the plane GEMMs (conv_p3.hip) only
@@ -401,6 +410,9 @@ class ConvBN(_BatchNorm):
             if want_gres:
                 gres = empty_act((N, P, Q, C), dev)
             relu_mode = (1 if had_res else 2) if self.relu else 0
+            if self.relu6:
+                assert not had_res, "ReLU6 layers take no residual"
+                relu_mode = 3
             if Fn.native(dy):
                 self._bn_backward_acc(dy, y, z, saved, relu_mode, dz, gres)
             else:
@@ -432,6 +444,107 @@ class ConvBN(_BatchNorm):
     def clear(self):
         self._saved = None
         self._pre_reduced = False
+
+
+class DepthwiseConvBN(_BatchNorm):
+    """depthwise conv 3x3 (stride 1 | 2, 'SAME') -> BatchNorm(train) -> ReLU6: the middle layer of a
+    MobileNet-v2 bottleneck. One fp32 [C,3,3] kernel per channel, no GEMM: the GPU path is the
+    stencil kernels of csrc/kernels/dwconv.hip on PLAIN activations (16-bit, or fp32 tensors on the
+    fp32 path -- never Planes), with the BN statistics accumulated by the forward kernel; the BN
+    apply then writes the next 1x1 GEMM's operand (Planes on the fp32 path) as ConvBN does. Backward:
+    BN backward (ReLU6 mask recomputed from z) into a plain dz, the two-stage weight gradient
+    (through run_wgrad: side-stream capable), the gather data gradient."""
+
+    relu = True
+    relu6 = True
+
+    def __init__(self, ps: ParamStore, name: str, in_shape, stride: int = 1, eps: float = 1e-5, decay: float = 0.9):
+        H, W, C = in_shape
+        assert C % 8 == 0 and stride in (1, 2)
+        self.name = name
+        self.in_shape = in_shape
+        self.stride = stride
+        pt, pb, pl, pr = resolve_pads("SAME", H, W, 3, 3, stride, stride)
+        assert pt in (0, 1) and pl in (0, 1)
+        self.pads = (pt, pb, pl, pr)
+        self.out_shape = ((H + pt + pb - 3) // stride + 1, (W + pl + pr - 3) // stride + 1, C)
+        self.eps = eps
+        self.decay = decay
+        self.w = ps.add(f"{name}/depthwise/kernel", (C, 3, 3), True, ps.variance_scaling(9))
+        self._init_bn(ps, name, C)
+        self._saved = None
+        self._ws = None  # weight-gradient workspace [blocks][9][C], sized at the first backward
+        self.training = True
+
+    def flops(self, batch: int) -> int:
+        P, Q, C = self.out_shape
+        return 2 * batch * P * Q * C * 9
+
+    def params(self):
+        return [self.w, self.beta, self.gamma]
+
+    def bwd_fuse_request(self):
+        return None  # its BN backward reduction always runs in bn_bwd_reduce_acc
+
+    def _conv(self, x, z, **kw):
+        pt, _, pl, _ = self.pads
+        return Fn.dwconv_forward(x, self.w.data, z, self.stride, pt, pl, **kw)
+
+    def forward(self, x, out=None):
+        if Fn.is_planes(x):  # (a producer that wrote the GEMM format: the stencil reads plain fp32)
+            x = Fn.from_planes(x)
+        N = x.shape[0]
+        P, Q, C = self.out_shape
+        dev = x.device
+        z = empty_act((N, P, Q, C), dev)
+        if not self.training:
+            y = out if out is not None else empty_op((N, P, Q, C), dev)
+            self._conv(x, z)
+            self._saved = None
+            return self._bn_inference(z, y)
+        if Fn.native(x):
+            y = out if out is not None else empty_op((N, P, Q, C), dev)
+            acc_f, _, R = self._stat_bufs(N, dev)
+            # statistics from the stencil kernel: replica = row block % R; in deterministic mode its
+            # grid is capped at the R = det_replicas row blocks, so every slot receives one add
+            self._conv(x, z, stats=acc_f, stats_R=R, stats_shift=self._shift())
+            saved = self._bn_forward_acc(z, y)
+        else:
+            y = out if out is not None else empty_act((N, P, Q, C), dev)
+            self._conv(x, z)
+            saved = self._bn_forward_ref(z, y)
+        self._saved = (x, z, y, saved)
+        return y
+
+    def _wgrad(self, dz, x):
+        pt, _, pl, _ = self.pads
+        if Fn.native(dz) and self._ws is None:
+            self._ws = Fn.dwconv_wgrad_workspace(x.shape, dz.shape, dz.device)
+        Fn.dwconv_wgrad(dz, x, self.w.grad, self.stride, pt, pl, ws=self._ws)
+
+    def backward(self, dy, dx=None, accumulate: bool = False):
+        """Returns dx. ``accumulate``: add into ``dx`` (an identity shortcut's gradient)."""
+        x, z, y, saved = self._saved
+        dev = dy.device
+        N = dy.shape[0]
+        P, Q, C = self.out_shape
+        dz = empty_act((N, P, Q, C), dev)  # plain: the stencil kernels consume it
+        if Fn.native(dy):  # (mode 3: the ReLU6 mask recomputed from z)
+            self._bn_backward_acc(dy, None, z, saved, 3, dz)
+        else:
+            self._bn_backward_ref(dy, y, z, saved, 3, dz)
+        run_wgrad(self, dz, x)
+        H, W, _ = self.in_shape
+        if dx is None:
+            dx = empty_act((N, H, W, C), dev)
+            accumulate = False
+        pt, _, pl, _ = self.pads
+        Fn.dwconv_dgrad(dz, self.w.data, dx, self.stride, pt, pl, accumulate)
+        self._saved = None
+        return dx
+
+    def clear(self):
+        self._saved = None
 
 
 # Weight-gradient GEMMs on a side stream (set by the Trainer around a step, HCB_WGRAD_STREAM=1):

@@ -1004,6 +1004,86 @@ def conv_wgrad(dz, x, spec: ConvSpec, dw, cfg=None):
     return dw
 
 
+# ------------------------------------------------------------------- depthwise 3x3
+def dw_geom(x_shape, ldx: int, z_shape, ldz: int, stride: int, pt: int, pl: int):
+    """The int list the dwconv ops take: [N, H, W, C, ldx, P, Q, ldz, sh, sw, pt, pl]."""
+    N, H, W, C = x_shape
+    _, P, Q, _ = z_shape
+    return [N, H, W, C, ldx, P, Q, ldz, stride, stride, pt, pl]
+
+
+def _dw_pads(H, W, P, Q, stride, pt, pl):
+    """(pl, pr, pt, pb) of F.pad for a 3x3 window: bottom / right as the output size implies."""
+    return (pl, max((Q - 1) * stride + 3 - W - pl, 0), pt, max((P - 1) * stride + 3 - H - pt, 0))
+
+
+def _dw_ref_operands(x, w, z_shape, stride, pt, pl):
+    """NCHW padded input and [C, 1, 3, 3] weight of the F.conv2d(groups=C) reference form."""
+    _, H, W, C = x.shape
+    _, P, Q, _ = z_shape
+    xt = F.pad(x.permute(0, 3, 1, 2), _dw_pads(H, W, P, Q, stride, pt, pl))
+    Hn, Wn = (P - 1) * stride + 3, (Q - 1) * stride + 3  # rows / columns a window reaches
+    return xt[:, :, :Hn, :Wn], w.reshape(C, 1, 3, 3).to(x.dtype)
+
+
+def dwconv_forward(x, w, out, stride: int, pt: int, pl: int, stats=None, stats_R: int = 0, stats_shift=None):
+    """out[n,p,q,c] = sum_{r,s} x[n, p*stride-pt+r, q*stride-pl+s, c] * w[c,r,s]: depthwise 3x3, w the
+    fp32 [C,3,3] master (no pack). GPU (csrc/kernels/dwconv.hip): plain 16-bit or fp32 tensors (never
+    Planes), fp32 FMA; ``stats``: the BN statistics sum(out - shift), sum((out - shift)^2) accumulated
+    into stats_R replicas of [2][C] by row block, as conv_forward leaves them."""
+    if native(x):
+        assert not is_planes(x) and not is_planes(out), "the depthwise kernels read and write plain tensors"
+        _ext.ops().dwconv_fwd(x, w, out, dw_geom(x.shape, ld(x), out.shape, ld(out), stride, pt, pl), stats,
+                              int(stats_R), stats_shift)
+        return out
+    xt, wt = _dw_ref_operands(x, w, out.shape, stride, pt, pl)
+    out.copy_(F.conv2d(xt, wt, stride=stride, groups=x.shape[3]).permute(0, 2, 3, 1))
+    return out
+
+
+def dwconv_dgrad(dz, w, dx, stride: int, pt: int, pl: int, accumulate: bool = False):
+    """dx[N,H,W,C] (+)= conv_transpose(dz, w) of the depthwise 3x3 (GPU: gather form, no atomics)."""
+    if native(dz):
+        _ext.ops().dwconv_dgrad(dz, w, dx, dw_geom(dx.shape, ld(dx), dz.shape, ld(dz), stride, pt, pl),
+                                bool(accumulate))
+        return dx
+    N, H, W, C = dx.shape
+    _, P, Q, _ = dz.shape
+    Hn, Wn = (P - 1) * stride + 3, (Q - 1) * stride + 3
+    g = torch.nn.grad.conv2d_input((N, C, Hn, Wn), w.reshape(C, 1, 3, 3).to(dz.dtype), dz.permute(0, 3, 1, 2),
+                                   stride=stride, groups=C)
+    g = F.pad(g, (0, max(W + pl - Wn, 0), 0, max(H + pt - Hn, 0)))  # rows / columns no window reaches
+    g = g[:, :, pt:pt + H, pl:pl + W].permute(0, 2, 3, 1)
+    if accumulate:
+        dx.add_(g)
+    else:
+        dx.copy_(g)
+    return dx
+
+
+def dwconv_wgrad_workspace(x_shape, z_shape, device):
+    """The caller-owned workspace [blocks][9][C] of dwconv_wgrad's first stage (never zeroed)."""
+    blocks = _ext.ops().dwconv_wgrad_blocks(dw_geom(x_shape, x_shape[3], z_shape, z_shape[3], 1, 0, 0))
+    return torch.empty((blocks, 9, x_shape[3]), dtype=torch.float32, device=device)
+
+
+def dwconv_wgrad(dz, x, dw, stride: int, pt: int, pl: int, ws=None):
+    """dw[c,r,s] (fp32) = sum_{n,p,q} dz[n,p,q,c] * x[n, p*stride-pt+r, q*stride-pl+s, c]. GPU: two
+    stages without atomics -- slab partials into ``ws`` (dwconv_wgrad_workspace), then a fold in
+    fixed order that STORES dw: bitwise reproducible in every mode. The reference path adds into dw
+    (a zeroed gradient slot), as conv_wgrad does."""
+    if native(dz):
+        if ws is None:
+            ws = dwconv_wgrad_workspace(x.shape, dz.shape, dz.device)
+        _ext.ops().dwconv_wgrad(dz, x, ws, dw, dw_geom(x.shape, ld(x), dz.shape, ld(dz), stride, pt, pl))
+        return dw
+    C = x.shape[3]
+    xt, _ = _dw_ref_operands(x, dw, dz.shape, stride, pt, pl)
+    g = torch.nn.grad.conv2d_weight(xt, (C, 1, 3, 3), dz.permute(0, 3, 1, 2), stride=stride, groups=C)
+    dw.add_(g.reshape(dw.shape).to(dw.dtype))
+    return dw
+
+
 # --------------------------------------------------------------------------- BN
 class BNSaved:
     __slots__ = ("mean", "invstd")
@@ -1050,7 +1130,20 @@ def conv_bn_inference(x, spec: ConvSpec, wpack, w_master, gamma, beta, running_m
     return out
 
 
-def bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu: bool, residual=None):
+def _clip(y, relu: bool, act_max):
+    """act(y) of the reference paths: ReLU, with the upper clip ``act_max`` (ReLU6: 6.0) when given."""
+    assert act_max is None or relu, "act_max clips a ReLU"
+    if not relu:
+        return y
+    return torch.relu(y) if act_max is None else torch.clamp(y, 0.0, float(act_max))
+
+
+def _amax_kw(act_max) -> dict:
+    """The trailing op argument of the BN apply kernels (absent: exactly the call without it)."""
+    return {} if act_max is None else {"act_max": float(act_max)}
+
+
+def bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu: bool, residual=None, act_max=None):
     """Inference BN (``--forward_only``: tf_cnn_benchmarks builds the model with
     phase_train=False): out = act(gamma*(z-moving_mean)/sqrt(moving_var+eps) + beta [+ res]).
     A BN without a producing GEMM (ResNet v2's pre-activation, ``BNReLU``) and the unfused form of
@@ -1072,21 +1165,22 @@ def bn_inference(z, gamma, beta, running_mean, running_var, eps, out, relu: bool
                 residual = from_planes(residual)
         _ext.ops().bn_apply_acc(z, ld(z), _pl(out), ld(out), _pl(residual), ld(residual) if residual is not None else 0,
                                 M, C, acc, 1, eps, 1.0, gamma, beta, 1 if relu else 0, scratch[0], scratch[1],
-                                None, None, running_mean)
+                                None, None, running_mean, **_amax_kw(act_max))
         return out
     invstd = torch.rsqrt(running_var + eps)
     if native(z):
         _ext.ops().bn_apply(z, ld(z), out, ld(out), residual, ld(residual) if residual is not None else 0,
-                            N * H * W, C, running_mean, invstd, gamma, beta, 1 if relu else 0)
+                            N * H * W, C, running_mean, invstd, gamma, beta, 1 if relu else 0, **_amax_kw(act_max))
         return out
     y = (z - running_mean) * (invstd * gamma) + beta
     if residual is not None:
         y = y + residual
-    out.copy_(torch.relu(y) if relu else y)
+    out.copy_(_clip(y, relu, act_max))
     return out
 
 
-def bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, out, relu: bool, residual=None):
+def bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, out, relu: bool, residual=None,
+               act_max=None):
     """Training BN, the PyTorch reference path (CPU, and the GPU's reference-precision dtypes): batch
     stats, running-stat update, out = act(gamma*xhat + beta [+ residual]). A native tensor takes
     bn_stats_acc (or the producing conv's epilogue) + bn_forward_acc."""
@@ -1107,26 +1201,25 @@ def bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, out, re
     y = (z.to(mean.dtype) - mean) * (invstd * gamma) + beta
     if residual is not None:
         y = y + residual
-    if relu:
-        y = torch.relu(y)
-    out.copy_(y)
+    out.copy_(_clip(y, relu, act_max))
     return BNSaved(mean, invstd)
 
 
 def bn_forward_acc(z, gamma, beta, running_mean, running_var, momentum, eps, out, relu: bool, acc, R: int,
-                   saved_mean, saved_invstd, residual=None, shift=None, res_bn=None):
+                   saved_mean, saved_invstd, residual=None, shift=None, res_bn=None, act_max=None):
     """GPU BN forward whose batch statistics were accumulated by the producing conv's epilogue
     into ``acc`` (R replicas of [2][C]); mean/invstd are derived inside the apply kernel (no
     finalize launch) and written to saved_mean / saved_invstd for the backward. ``shift``:
     the per-channel offset the producing conv subtracted before accumulating (conv_forward).
     ``res_bn`` = (acc, gamma, beta, saved_mean, saved_invstd, running_mean, running_var, shift) of a
     second BN applied to ``residual`` in the same pass (a projection shortcut's raw conv output:
-    its normalised tensor is never written); same M, C and replica count R."""
+    its normalised tensor is never written); same M, C and replica count R. ``act_max``: the ReLU's
+    upper clip (ReLU6: 6.0)."""
     N, H, W, C = z.shape
     M = N * H * W
     _ext.ops().bn_apply_acc(z, ld(z), _pl(out), ld(out), _pl(residual), ld(residual) if residual is not None else 0,
                             M, C, acc, R, eps, momentum, gamma, beta, 1 if relu else 0, saved_mean, saved_invstd,
-                            running_mean, running_var, shift, *(res_bn or ()))
+                            running_mean, running_var, shift, *(res_bn or ()), **_amax_kw(act_max))
     return BNSaved(saved_mean, saved_invstd)
 
 
@@ -1194,7 +1287,8 @@ def bn_backward_acc(dy, y, z, saved: BNSaved, gamma, beta, relu_mode: int, dgamm
 
 def bn_backward(dy, y, z, saved: BNSaved, gamma, beta, relu_mode: int, dgamma, dbeta, dz, gres=None):
     """BN(+ReLU) backward. relu_mode: 0 none, 1 mask from stored output y (residual blocks),
-    2 mask recomputed from z. Writes dgamma/dbeta (fp32, overwrite), dz, and optionally the
+    2 mask recomputed from z, 3 ReLU6: recomputed from z, the gradient passes where 0 < bn(z) < 6
+    (strict at both ends). Writes dgamma/dbeta (fp32, overwrite), dz, and optionally the
     masked upstream gradient gres (the residual branch's gradient). The PyTorch reference path, as
     bn_forward is; a native tensor takes bn_backward_acc."""
     assert not native(z), "native BN backward: bn_backward_acc"
@@ -1209,6 +1303,9 @@ def bn_backward(dy, y, z, saved: BNSaved, gamma, beta, relu_mode: int, dgamma, d
         g = dy * (y > 0).to(dy.dtype)
     elif relu_mode == 2:
         g = dy * ((xhat * gamma + beta) > 0).to(dy.dtype)
+    elif relu_mode == 3:
+        v = xhat * gamma + beta
+        g = dy * ((v > 0) & (v < 6)).to(dy.dtype)
     gf = g.reshape(-1, C) if g.is_contiguous() else g.contiguous().reshape(-1, C)
     xf = xhat.reshape(-1, C)
     db = gf.sum(0)

@@ -446,9 +446,15 @@ void conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, at::IntArra
   hcb::launch_conv_wgrad(p, (int)cfg, eff_splits, cur_stream());
 }
 
+// the BN apply kernels' activation code: 0 none, 1 ReLU, 2 ReLU with the upper clip act_max (ReLU6)
+int relu_code(int64_t relu, const c10::optional<double>& act_max) {
+  TORCH_CHECK(!act_max.has_value() || (relu != 0 && *act_max > 0.0), "hcb.bn_apply: act_max clips a ReLU at a positive value");
+  return relu == 0 ? 0 : (act_max.has_value() ? 2 : 1);
+}
+
 void bn_apply(const Tensor& x, int64_t ldx, const Tensor& y, int64_t ldy, const c10::optional<Tensor>& res,
               int64_t ldr, int64_t M, int64_t C, const Tensor& mean, const Tensor& invstd,
-              const Tensor& gamma, const Tensor& beta, int64_t relu) {
+              const Tensor& gamma, const Tensor& beta, int64_t relu, c10::optional<double> act_max) {
   check_act(x, "x");
   check_act(y, "y");
   TORCH_CHECK(C % 8 == 0 && C <= 2048 && ldx % 8 == 0 && ldy % 8 == 0, "hcb.bn_apply: C/ld");
@@ -463,7 +469,7 @@ void bn_apply(const Tensor& x, int64_t ldx, const Tensor& y, int64_t ldy, const 
   }
   hcb::launch_bn_apply(x.data_ptr(), (int)ldx, y.data_ptr(), (int)ldy, rp, (int)ldr, (int)M, (int)C,
                        mean.data_ptr<float>(), invstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                       beta.data_ptr<float>(), (int)relu, cur_stream());
+                       beta.data_ptr<float>(), relu_code(relu, act_max), cur_stream(), (float)act_max.value_or(0.0));
 }
 
 // geom = [N,H,W,C,P,Q,ldy,kh,kw,sh,sw,ph,pw]; z contiguous [N,H,W,C]
@@ -804,7 +810,8 @@ void bn_apply_acc(const Tensor& x, int64_t ldx, const Tensor& y, int64_t ldy, co
                   const c10::optional<Tensor>& shift, const c10::optional<Tensor>& res_acc, const c10::optional<Tensor>& res_gamma,
                   const c10::optional<Tensor>& res_beta, const c10::optional<Tensor>& res_saved_mean,
                   const c10::optional<Tensor>& res_saved_invstd, const c10::optional<Tensor>& res_rm,
-                  const c10::optional<Tensor>& res_rv, const c10::optional<Tensor>& res_shift) {
+                  const c10::optional<Tensor>& res_rv, const c10::optional<Tensor>& res_shift,
+                  c10::optional<double> act_max) {
   const bool f32 = check_act_or_f32(x, "x");
   // fp32 z with a bf16 y: y is written as [3, ...] bf16 planes; a bf16 residual is planes too
   const bool yp3 = f32 && y.scalar_type() == at::kBFloat16;
@@ -848,10 +855,11 @@ void bn_apply_acc(const Tensor& x, int64_t ldx, const Tensor& y, int64_t ldy, co
   }
   hcb::launch_bn_apply_acc(x.data_ptr(), (int)ldx, y.data_ptr(), (int)ldy, rp, (int)ldr, (int)M, (int)C,
                            acc.data_ptr<float>(), (int)R, (float)eps, (float)momentum, gamma.data_ptr<float>(),
-                           beta.data_ptr<float>(), (int)relu, saved_mean.data_ptr<float>(),
+                           beta.data_ptr<float>(), relu_code(relu, act_max), saved_mean.data_ptr<float>(),
                            saved_invstd.data_ptr<float>(), rm.has_value() ? rm->data_ptr<float>() : nullptr,
                            rv.has_value() ? rv->data_ptr<float>() : nullptr, opt_f32(shift, C, "shift"),
-                           res_acc.has_value() ? &rb : nullptr, cur_stream(), f32, yps, rps);
+                           res_acc.has_value() ? &rb : nullptr, cur_stream(), f32, yps, rps,
+                           (float)act_max.value_or(0.0));
 }
 
 // pooled-gradient source (pool_amax / pool_geom = [H, W, P, Q, k, s, pt, pl]): dy is the max-pool
@@ -979,6 +987,79 @@ void bn_stats_acc(const Tensor& x, int64_t ldx, int64_t M, int64_t C, const Tens
   check_range(x, ((M - 1) * ldx + C) * (f32 ? 4 : 2), "x");
   hcb::launch_bn_stats_acc(x.data_ptr(), (int)ldx, (int)M, (int)C, opt_f32(shift, C, "shift"), acc.data_ptr<float>(),
                            (int)R, cur_stream(), f32);
+}
+
+// ---- depthwise 3x3 conv (dwconv.hip). geom = [N, H, W, C, ldx, P, Q, ldz, sh, sw, pt, pl]: x / dx
+// [N,H,W,C] with row stride ldx, z / dz [N,P,Q,C] with row stride ldz, w fp32 [C,3,3]
+hcb::DwParams dw_params(at::IntArrayRef g, const Tensor& x, const Tensor& z, const Tensor& w, bool* f32,
+                        const char* op) {
+  TORCH_CHECK(g.size() == 12, "hcb.", op, ": geom = [N, H, W, C, ldx, P, Q, ldz, sh, sw, pt, pl]");
+  *f32 = check_act_or_f32(x, "x");
+  same_act(x, z, "z");
+  check_f32(w, "w");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], P = g[5], Q = g[6], ldz = g[7];
+  const int64_t sh = g[8], sw = g[9], pt = g[10], pl = g[11];
+  const int64_t e = *f32 ? 4 : 2;
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1 && P >= 1 && Q >= 1, "hcb.", op, ": empty tensor");
+  TORCH_CHECK(C >= 8 && C % 8 == 0, "hcb.", op, ": C must be a multiple of 8, got ", C);
+  TORCH_CHECK(ldx % 8 == 0 && ldz % 8 == 0 && ldx >= C && ldz >= C, "hcb.", op, ": row strides (multiples of 8, >= C)");
+  TORCH_CHECK(sh == sw && (sh == 1 || sh == 2), "hcb.", op, ": stride 1 or 2");
+  TORCH_CHECK(pt >= 0 && pt <= 1 && pl >= 0 && pl <= 1, "hcb.", op, ": top / left pads in {0, 1}");
+  TORCH_CHECK((P - 1) * sh - pt < H && (Q - 1) * sw - pl < W, "hcb.", op, ": output larger than the padded input allows");
+  const int64_t xb = ((N * H * W - 1) * ldx + C) * e, zb = ((N * P * Q - 1) * ldz + C) * e;
+  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31), "hcb.", op, ": tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(z, zb, "z");
+  TORCH_CHECK(w.is_contiguous() && w.numel() == 9 * C, "hcb.", op, ": w must be contiguous fp32 [C, 3, 3]");
+  check_align16(x.data_ptr(), "x");
+  check_align16(z.data_ptr(), "z");
+  check_align16(w.data_ptr(), "w");
+  hcb::DwParams p{};
+  p.x = x.data_ptr();
+  p.z = z.data_ptr();
+  p.w = w.data_ptr<float>();
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx;
+  p.P = (int)P; p.Q = (int)Q; p.ldz = (int)ldz; p.S = (int)sh; p.pt = (int)pt; p.pl = (int)pl;
+  return p;
+}
+
+void dwconv_fwd(const Tensor& x, const Tensor& w, const Tensor& z, at::IntArrayRef g,
+                const c10::optional<Tensor>& stats, int64_t R, const c10::optional<Tensor>& shift) {
+  bool f32;
+  hcb::DwParams p = dw_params(g, x, z, w, &f32, "dwconv_fwd");
+  if (stats.has_value()) {
+    TORCH_CHECK(R >= 1, "hcb.dwconv_fwd: stats_R");
+    p.stats = const_cast<float*>(opt_f32(stats, R * 2 * p.C, "stats"));
+    p.R = (int)R;
+    p.shift = opt_f32(shift, p.C, "stats_shift");
+  }
+  hcb::launch_dwconv_fwd(p, cur_stream(), f32);
+}
+
+void dwconv_dgrad(const Tensor& dz, const Tensor& w, const Tensor& dx, at::IntArrayRef g, bool accumulate) {
+  bool f32;
+  hcb::DwParams p = dw_params(g, dx, dz, w, &f32, "dwconv_dgrad");
+  p.accumulate = accumulate ? 1 : 0;
+  hcb::launch_dwconv_dgrad(p, cur_stream(), f32);
+}
+
+int64_t dwconv_wgrad_blocks(at::IntArrayRef g) {
+  TORCH_CHECK(g.size() == 12 && g[3] >= 8 && g[3] % 8 == 0 && g[0] * g[5] * g[6] >= 1 &&
+                  g[0] * g[5] * g[6] < (1ll << 31), "hcb.dwconv_wgrad_blocks: geom");
+  return hcb::dwconv_wgrad_blocks((int)g[0], (int)g[5], (int)g[6], (int)g[3]);
+}
+
+void dwconv_wgrad(const Tensor& dz, const Tensor& x, const Tensor& ws, const Tensor& dw, at::IntArrayRef g) {
+  bool f32;
+  check_f32(dw, "dw");
+  hcb::DwParams p = dw_params(g, x, dz, dw, &f32, "dwconv_wgrad");  // (dw checked as the [C, 3, 3] weight is)
+  p.w = nullptr;
+  check_f32(ws, "ws");
+  const int64_t nblk = hcb::dwconv_wgrad_blocks(p.N, p.P, p.Q, p.C);
+  TORCH_CHECK(ws.is_contiguous() && ws.numel() >= nblk * 9 * p.C, "hcb.dwconv_wgrad: the workspace holds ", ws.numel(),
+              " floats, this problem needs ", nblk * 9 * p.C, " (dwconv_wgrad_blocks * 9 * C)");
+  check_align16(ws.data_ptr(), "ws");
+  hcb::launch_dwconv_wgrad(p, ws.data_ptr<float>(), (int)nblk, dw.data_ptr<float>(), cur_stream(), f32);
 }
 
 void relu_bwd(const Tensor& dy, const Tensor& y, const Tensor& dz) {
@@ -1407,7 +1488,7 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
   m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);
   m.def("conv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int[] geom, int cfg, int splits) -> ()");
-  m.def("bn_apply(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu) -> ()");
+  m.def("bn_apply(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu, float? act_max=None) -> ()");
   m.def("pool_fwd(Tensor x, Tensor(a!) y, Tensor(b!)? idx, int[] geom) -> ()");
   m.def("pool_bwd(Tensor dy, Tensor x, Tensor y, Tensor? idx, Tensor(a!) dx, int[] geom, bool accumulate) -> ()");
   m.def("pool_fwd_p3(Tensor x, Tensor(a!) y, Tensor(b!)? idx, int[] geom) -> ()");
@@ -1427,10 +1508,14 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("weight_pack(Tensor master, Tensor(a!) pack, Tensor table, int max_work, int lo=0) -> ()");
   m.def("add_bf16(Tensor a, Tensor b, Tensor(a!) y) -> ()");
   m.def("relu_bwd(Tensor dy, Tensor y, Tensor(a!) dz) -> ()");
-  m.def("bn_apply_acc(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor acc, int R, float eps, float momentum, Tensor gamma, Tensor beta, int relu, Tensor(b!) saved_mean, Tensor(c!) saved_invstd, Tensor(d!)? running_mean, Tensor(e!)? running_var, Tensor? shift=None, Tensor? res_acc=None, Tensor? res_gamma=None, Tensor? res_beta=None, Tensor(g!)? res_saved_mean=None, Tensor(h!)? res_saved_invstd=None, Tensor(i!)? res_running_mean=None, Tensor(j!)? res_running_var=None, Tensor? res_shift=None) -> ()");
+  m.def("bn_apply_acc(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor acc, int R, float eps, float momentum, Tensor gamma, Tensor beta, int relu, Tensor(b!) saved_mean, Tensor(c!) saved_invstd, Tensor(d!)? running_mean, Tensor(e!)? running_var, Tensor? shift=None, Tensor? res_acc=None, Tensor? res_gamma=None, Tensor? res_beta=None, Tensor(g!)? res_saved_mean=None, Tensor(h!)? res_saved_invstd=None, Tensor(i!)? res_running_mean=None, Tensor(j!)? res_running_var=None, Tensor? res_shift=None, float? act_max=None) -> ()");
   m.def("bn_bwd_reduce_acc(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu, Tensor(a!) acc, int R, Tensor(b!)? gout, int ldg, Tensor? pool_amax=None, int[]? pool_geom=None) -> ()");
   m.def("bn_bwd_apply_acc(Tensor dy, int lddy, Tensor? y, int ldyv, Tensor x, int ldx, Tensor(a!) dx, int lddx, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, Tensor acc, int R, Tensor(b!) dgamma, Tensor(c!) dbeta, int relu, Tensor(d!)? shift_out=None, Tensor? pool_amax=None, int[]? pool_geom=None, Tensor? add=None, int ldadd=0) -> ()");
   m.def("bn_stats_acc(Tensor x, int ldx, int M, int C, Tensor(a!) acc, int R, Tensor? shift=None) -> ()");
+  m.def("dwconv_fwd(Tensor x, Tensor w, Tensor(a!) z, int[] geom, Tensor(b!)? stats=None, int stats_R=0, Tensor? stats_shift=None) -> ()");
+  m.def("dwconv_dgrad(Tensor dz, Tensor w, Tensor(a!) dx, int[] geom, bool accumulate) -> ()");
+  m.def("dwconv_wgrad(Tensor dz, Tensor x, Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
+  m.def("dwconv_wgrad_blocks(int[] geom) -> int", dwconv_wgrad_blocks);
   m.def("preprocess_images(Tensor src, Tensor desc, Tensor desc_host, Tensor(a!) out, float[] scale, float[] bias) -> ()");
   m.def("preprocess_distort(Tensor src, Tensor desc, Tensor desc_host, Tensor params, Tensor params_host, "
         "Tensor(a!) out, Tensor(b!) work, float[] scale, float[] bias) -> ()");
@@ -1489,6 +1574,9 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("bn_bwd_reduce_acc", bn_bwd_reduce_acc);
   m.impl("bn_bwd_apply_acc", bn_bwd_apply_acc);
   m.impl("bn_stats_acc", bn_stats_acc);
+  m.impl("dwconv_fwd", dwconv_fwd);
+  m.impl("dwconv_dgrad", dwconv_dgrad);
+  m.impl("dwconv_wgrad", dwconv_wgrad);
   m.impl("synth_images", synth_images);
   m.impl("dropout_fwd", dropout_fwd);
   m.impl("bn_relu_maxpool_acc", bn_relu_maxpool_acc);

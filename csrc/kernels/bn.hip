@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
                                                        const uint16_t* __restrict__ res, int ldr,
                                                        int M, int C, const float* mean,
                                                        const float* invstd, const float* gamma,
-                                                       const float* beta, int relu) {
+                                                       const float* beta, int relu, float amax) {
   RowMap rm = rowmap(C);
   if (!rm.active) return;
   float sc[8], sh[8];
@@ -100,6 +100,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
       if (relu) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+        if (relu == 2) {  // upper clip (ReLU6)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] = fminf(f[e], amax);
+        }
       }
       if (m < M) *reinterpret_cast<u32x4*>(y + (size_t)m * ldy + rm.cv * 8) = pack8(f);
     }
@@ -147,7 +151,9 @@ __device__ __forceinline__ void pool_gather(const PoolSrc& ps, int m, int M, int
 // type of the ReLU-mask source y -- T, or (fp32 path) uint16_t: the bf16 hi plane of the plane-stored
 // activation (hi > 0 exactly when y > 0 for every normal y).
 // relu: 0 = none, 1 = mask from stored output y (y > 0), 2 = mask recomputed from x
-// (gamma*xhat + beta > 0; valid when the block had no residual add)
+// (gamma*xhat + beta > 0; valid when the block had no residual add), 3 = ReLU6: recomputed from x,
+// the gradient passes where 0 < gamma*xhat + beta < 6 (strict at both ends; reduce and apply share
+// this one predicate)
 template <typename T, typename TY = T, bool POOL = false>
 struct BwdSrcT {
   __amdgpu_buffer_rsrc_t dyr, xr, yr;
@@ -181,6 +187,12 @@ __device__ __forceinline__ void bwd_math_t(const Act8<T>& dv, const Act8<T>& xvv
   } else if (relu == 2) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) g[e] = (xv[e] * sc[e] + sh[e]) > 0.f ? d[e] : 0.f;
+  } else if (relu == 3) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float v = xv[e] * sc[e] + sh[e];
+      g[e] = (v > 0.f && v < 6.f) ? d[e] : 0.f;
+    }
   } else {
 #pragma unroll
     for (int e = 0; e < 8; ++e) g[e] = d[e];
@@ -197,10 +209,10 @@ static int bn_grid(int M, int C) {
 
 void launch_bn_apply(const void* x, int ldx, void* y, int ldy, const void* res, int ldr, int M,
                      int C, const float* mean, const float* invstd, const float* gamma,
-                     const float* beta, int relu, hipStream_t st) {
+                     const float* beta, int relu, hipStream_t st, float act_max) {
   hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_grid(M, C)), dim3(256), 0, st, (const uint16_t*)x,
                      ldx, (uint16_t*)y, ldy, (const uint16_t*)res, ldr, M, C, mean, invstd, gamma,
-                     beta, relu);
+                     beta, relu, act_max);
 }
 
 // =======================================================================================
@@ -308,7 +320,8 @@ __global__ __launch_bounds__(256) void bn_apply_acc_kernel(
     const T* __restrict__ x, int ldx, void* __restrict__ yv, int ldy, const void* __restrict__ resv,
     int ldr, int M, int C, int CVB, const float* __restrict__ acc, int R, float eps, float momentum,
     const float* __restrict__ gamma, const float* __restrict__ beta, int relu, float* saved_mean,
-    float* saved_invstd, float* run_mean, float* run_var, const float* shift, ResBN rb, int64_t yps, int64_t rps) {
+    float* saved_invstd, float* run_mean, float* run_var, const float* shift, ResBN rb, int64_t yps, int64_t rps,
+    float amax) {
   constexpr bool RP3 = P3 && !RBN;  // residual planes
   T* __restrict__ y = reinterpret_cast<T*>(yv);
   const T* __restrict__ res = reinterpret_cast<const T*>(resv);
@@ -395,6 +408,10 @@ __global__ __launch_bounds__(256) void bn_apply_acc_kernel(
       if (relu) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+        if (relu == 2) {  // upper clip (ReLU6)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] = fminf(f[e], amax);
+        }
       }
       if (m < M) {
         if constexpr (P3)
@@ -729,26 +746,28 @@ template <typename T, bool P3 = false>
 static void bn_apply_acc_t(const void* x, int ldx, void* y, int ldy, const void* res, int ldr, int M, int C,
                            const float* acc, int R, float eps, float momentum, const float* gamma, const float* beta,
                            int relu, float* saved_mean, float* saved_invstd, float* run_mean, float* run_var,
-                           const float* shift, const ResBN* res_bn, hipStream_t st, int64_t yps, int64_t rps) {
+                           const float* shift, const ResBN* res_bn, hipStream_t st, int64_t yps, int64_t rps,
+                           float amax) {
   int cvb;
   dim3 grid = bn_grid_groups(M, C, &cvb);
   const ResBN rb = res_bn != nullptr ? *res_bn : ResBN{};
   if (res_bn != nullptr)
     hipLaunchKernelGGL((bn_apply_acc_kernel<true, T, P3>), grid, dim3(256), (size_t)4 * cvb * 8 * 4, st, (const T*)x,
                        ldx, y, ldy, res, ldr, M, C, cvb, acc, R, eps, momentum, gamma, beta, relu, saved_mean,
-                       saved_invstd, run_mean, run_var, shift, rb, yps, rps);
+                       saved_invstd, run_mean, run_var, shift, rb, yps, rps, amax);
   else
     hipLaunchKernelGGL((bn_apply_acc_kernel<false, T, P3>), grid, dim3(256), (size_t)2 * cvb * 8 * 4, st, (const T*)x,
                        ldx, y, ldy, res, ldr, M, C, cvb, acc, R, eps, momentum, gamma, beta, relu, saved_mean,
-                       saved_invstd, run_mean, run_var, shift, rb, yps, rps);
+                       saved_invstd, run_mean, run_var, shift, rb, yps, rps, amax);
 }
 void launch_bn_apply_acc(const void* x, int ldx, void* y, int ldy, const void* res, int ldr, int M, int C,
                          const float* acc, int R, float eps, float momentum, const float* gamma, const float* beta,
                          int relu, float* saved_mean, float* saved_invstd, float* run_mean, float* run_var,
-                         const float* shift, const ResBN* res_bn, hipStream_t st, bool f32, int64_t yps, int64_t rps) {
+                         const float* shift, const ResBN* res_bn, hipStream_t st, bool f32, int64_t yps, int64_t rps,
+                         float act_max) {
   auto fn = yps > 0 ? bn_apply_acc_t<float, true> : (f32 ? bn_apply_acc_t<float> : bn_apply_acc_t<uint16_t>);
   fn(x, ldx, y, ldy, res, ldr, M, C, acc, R, eps, momentum, gamma, beta, relu, saved_mean, saved_invstd, run_mean,
-     run_var, shift, res_bn, st, yps, rps);
+     run_var, shift, res_bn, st, yps, rps, act_max);
 }
 
 void launch_bn_relu_maxpool_acc(const void* z, int N, int H, int W, int C, void* y, int P, int Q, int ldy, void* amax,

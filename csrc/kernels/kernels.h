@@ -141,7 +141,8 @@ void launch_gap_fwd_p3(const uint16_t* x, int64_t xps, uint16_t* y, int64_t yps,
 // y = act(gamma*(x-mean)*invstd + beta [+ res]) from a given mean / invstd, 16-bit data (inference)
 void launch_bn_apply(const void* x, int ldx, void* y, int ldy, const void* res, int ldr, int M,
                      int C, const float* mean, const float* invstd, const float* gamma,
-                     const float* beta, int relu, hipStream_t st);
+                     const float* beta, int relu, hipStream_t st, float act_max = 0.f);
+// (relu: 0 none, 1 max(v, 0), 2 min(max(v, 0), act_max) -- ReLU6 with act_max = 6)
 
 // finalize-free variants: statistics accumulated in R replicas of [2][C] (fp32 atomics).
 // Blocks tile (row split) x (channel group) so each block only reduces its group's replicas.
@@ -162,7 +163,7 @@ void launch_bn_apply_acc(const void* x, int ldx, void* y, int ldy, const void* r
                          const float* acc, int R, float eps, float momentum, const float* gamma, const float* beta,
                          int relu, float* saved_mean, float* saved_invstd, float* run_mean, float* run_var,
                          const float* shift, const ResBN* res_bn, hipStream_t st, bool f32 = false, int64_t yps = 0,
-                         int64_t rps = 0);
+                         int64_t rps = 0, float act_max = 0.f);
 // BN(acc statistics) + ReLU + max pool (NHWC, C contiguous): pooled y [N,P,Q] (row stride ldy) and
 // the uint8 window argmax [N,P,Q,C]; the BN+ReLU activation itself is not materialised
 void launch_bn_relu_maxpool_acc(const void* z, int N, int H, int W, int C, void* y, int P, int Q, int ldy, void* amax,
@@ -260,6 +261,27 @@ void launch_dropout_bwd(const void* dy, const uint8_t* mask, void* dx, int64_t n
 void launch_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t st);
 void launch_add_bf16(const void* a, const void* b, void* y, int64_t n, hipStream_t st);
 void launch_relu_bwd(const void* dy, const void* y, void* dz, int64_t n, hipStream_t st, bool f32 = false);
+
+// ---------------------------------------------------------------- depthwise 3x3 conv (dwconv.hip)
+// NHWC, T = the build's 16-bit type or fp32 (plain tensors), fp32 [C][3][3] weights, stride S in
+// {1, 2} (both directions), top / left pads in {0, 1}; bottom / right padding is whatever the output
+// size implies (out-of-range taps read zero). x [N,H,W] row stride ldx, z [N,P,Q] row stride ldz.
+struct DwParams {
+  const void* x;   // forward / weight gradient: the input; data gradient: dx (written)
+  const void* z;   // forward: the output (written); gradients: dz
+  const float* w;
+  int N, H, W, C, ldx, P, Q, ldz, S, pt, pl;
+  int CVB;         // channel vectors per block (set by the launcher)
+  int accumulate;  // data gradient: dx += instead of dx =
+  float* stats;    // forward: R replicas of [2][C] receiving sum(z - shift), sum((z - shift)^2), or null
+  int R;
+  const float* shift;
+};
+void launch_dwconv_fwd(const DwParams& p, hipStream_t st, bool f32);
+void launch_dwconv_dgrad(const DwParams& p, hipStream_t st, bool f32);
+// slabs of the weight gradient's first stage for this problem: the workspace holds blocks * 9 * C floats
+int dwconv_wgrad_blocks(int N, int P, int Q, int C);
+void launch_dwconv_wgrad(const DwParams& p, float* ws, int nblk, float* dw, hipStream_t st, bool f32);
 
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
