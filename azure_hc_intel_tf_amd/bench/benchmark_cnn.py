@@ -26,7 +26,35 @@ import torch
 from .flags import Params, compute_dtype_of, noop_flags_set, parse_flags
 
 MODEL_DEFAULT_BATCH = {"inception3": 32, "trivial": 32, "alexnet": 512, "googlenet": 32, "overfeat": 32,
-                       "lenet": 32, "vgg11": 32, "vgg16": 32, "vgg19": 32}
+                       "lenet": 32, "vgg11": 32, "vgg16": 32, "vgg19": 32,
+                       "resnet20": 128, "resnet32": 128, "resnet44": 128, "resnet56": 128, "resnet110": 128}
+# --data_name: images per training epoch (--num_epochs, the Num epochs line)
+DATASET_EPOCH_IMAGES = {"imagenet": 1281167, "cifar10": 50000}
+
+
+def check_dataset(p: Params) -> str:
+    """The dataset of a run (--data_name, default imagenet) and the model / flag combinations it refuses:
+    CIFAR-10 trains its own ResNets (and ``trivial``) at 32 x 32 and has neither colour distortion nor a
+    resize; those ResNets exist for CIFAR-10 only."""
+    from ..models import CIFAR_MODELS
+
+    name = p.data_name or "imagenet"
+    if name not in DATASET_EPOCH_IMAGES:
+        raise ValueError(f"--data_name={name}: the datasets are {', '.join(DATASET_EPOCH_IMAGES)}")
+    if name == "cifar10":
+        allowed = CIFAR_MODELS + ("trivial",)
+        if p.model not in allowed:
+            raise ValueError(f"--data_name=cifar10 runs the models {', '.join(allowed)}, not --model={p.model}")
+        if p.color_distortions:
+            raise ValueError("--color_distortions is an ImageNet preprocessing step: not with --data_name=cifar10")
+        if p.resize_method != "bilinear":
+            raise ValueError("--resize_method: CIFAR-10 images are never resized (not with --data_name=cifar10)")
+        if p.image_size and p.image_size != 32:
+            raise ValueError("--data_name=cifar10 images are 32 x 32: --image_size must be 32 or absent")
+    elif p.model in CIFAR_MODELS:
+        raise ValueError(f"--model={p.model} is a CIFAR-10 model: it needs --data_name=cifar10 "
+                         f"(CIFAR-10 models: {', '.join(CIFAR_MODELS)})")
+    return name
 
 
 def log_fn(msg: str = ""):
@@ -74,6 +102,8 @@ class BenchmarkCNN:
             raise ValueError("one process per MI355X: use --num_gpus=1 and launch one worker per GPU")
         if not 0.0 <= p.label_smoothing <= 1.0:
             raise ValueError("--label_smoothing must be in [0, 1]")
+        self.data_name = check_dataset(p)
+        self.epoch_images = DATASET_EPOCH_IMAGES[self.data_name]
         self.on_gpu = p.device == "gpu"
         if self.on_gpu and not torch.cuda.is_available():
             raise RuntimeError("--device=gpu but no GPU is visible (use --device=cpu for the CPU path)")
@@ -110,9 +140,13 @@ class BenchmarkCNN:
             self.compute_dtype = "fp32"
         if p.image_size:
             kw["image_size"] = p.image_size
+        if self.data_name == "cifar10":
+            from ..data.cifar10 import IMAGE_SIZE, NUM_CLASSES
+
+            kw["image_size"], kw["num_classes"] = IMAGE_SIZE, NUM_CLASSES
         self.model = create_model(p.model, **kw)
         if p.num_epochs:
-            self.num_batches = int(math.ceil(p.num_epochs * 1281167 / (self.batch_size * self.size)))
+            self.num_batches = int(math.ceil(p.num_epochs * self.epoch_images / (self.batch_size * self.size)))
         self.step_offset = 0
         if self.on_gpu and p.autotune and self.model.native:
             # per-shape kernel configs (cached in tuned/mi355x.json; new shapes timed once here)
@@ -132,6 +166,8 @@ class BenchmarkCNN:
         if p.init_learning_rate is not None:
             return constant_lr(p.init_learning_rate)
         gb = self.batch_size * self.size
+        if hasattr(self.model, "lr_schedule"):  # the model's own schedule (the CIFAR-10 ResNets)
+            return self.model.lr_schedule(gb)
         if self.model_name.startswith("resnet"):
             return resnet_lr_schedule(gb)
         # tf_cnn_benchmarks Model defaults: a constant rate scaled by global batch / the
@@ -196,9 +232,12 @@ class BenchmarkCNN:
         dev = [f"/gpu:{self.local_rank}"] if self.on_gpu else ["/cpu:0"]
         log_fn(f"Framework:   azure_hc_intel_tf_amd (PyTorch {torch.__version__}, HIP {torch.version.hip})")
         log_fn(f"Model:       {self.model_name}")
-        log_fn(f"Dataset:     imagenet ({'TFRecords ' + p.data_dir if p.data_dir else 'synthetic'})")
+        src = ("python pickles " if self.data_name == "cifar10" else "TFRecords ") + p.data_dir if p.data_dir else "synthetic"
+        log_fn(f"Dataset:     {self.data_name} ({src})")
         log_fn(f"Mode:        {'evaluation' if p.eval else 'forward-only' if p.forward_only else 'training'}")
-        if p.data_dir and not p.eval and not p.forward_only:
+        if p.data_dir and not p.eval and not p.forward_only and self.data_name == "cifar10":
+            log_fn("Distortions: " + ("pad 4 + random crop + flip" if p.distortions else "none"))
+        elif p.data_dir and not p.eval and not p.forward_only:
             log_fn("Distortions: " + (f"crop+flip{'+color' if p.color_distortions else ''}, resize={p.resize_method}"
                                       if p.distortions else "none (central crop), resize=bilinear"))
         log_fn(f"SingleSess:  False")
@@ -208,7 +247,7 @@ class BenchmarkCNN:
             log_fn("Num batches: one pass over the validation split")
         else:
             log_fn(f"Num batches: {self.num_batches}")
-            log_fn(f"Num epochs:  {self.num_batches * self.batch_size * self.size / 1281167:.2f}")
+            log_fn(f"Num epochs:  {self.num_batches * self.batch_size * self.size / self.epoch_images:.2f}")
         log_fn(f"Devices:     {dev}")
         log_fn(f"NUMA bind:   False")
         log_fn(f"Data format: {p.data_format} (logical; NHWC kernels)")
@@ -237,11 +276,25 @@ class BenchmarkCNN:
         from ..data.imagenet import ImageNetLoader
 
         p = self.params
+        if self.data_name == "cifar10":
+            from ..data.cifar10 import Cifar10Loader
+
+            return Cifar10Loader(p.data_dir, self.batch_size, self.device, rank=self.rank, world=self.size,
+                                 train=train, seed=p.tf_random_seed, loop=loop, distort=p.distortions)
         return ImageNetLoader(p.data_dir, self.batch_size, self.model.image_size, self.model.image_channels,
                               self.device, rank=self.rank, world=self.size, train=train, loop=loop,
                               seed=p.tf_random_seed, reader_threads=p.datasets_num_private_threads or 4,
                               decode_threads=p.num_decode_threads or 8, distort=p.distortions,
                               color=p.color_distortions, resize_method=p.resize_method)
+
+    def _files_word(self) -> str:
+        return "CIFAR-10 pickles" if self.data_name == "cifar10" else "TFRecord shards"
+
+    def _data_label(self, loader) -> str:
+        """The JSON summary's ``data`` field."""
+        if self.data_name == "cifar10":
+            return "cifar10-pickle" if loader else "cifar10-synthetic"
+        return "imagenet-tfrecord" if loader else "synthetic"
 
     def _sum_over_ranks(self, counts):
         """(examples, top-1 hits, top-5 hits) summed over the workers."""
@@ -298,7 +351,7 @@ class BenchmarkCNN:
         if p.data_dir:
             loader = self._loader(train=False, loop=not one_pass)
             if self.rank == 0:
-                log_fn(f"Reading {len(loader.files)} TFRecord shards from {p.data_dir}")
+                log_fn(f"Reading {len(loader.files)} {self._files_word()} from {p.data_dir}")
         self.loader = loader
         ckpt_step = None
         if p.train_dir:
@@ -409,7 +462,7 @@ class BenchmarkCNN:
             "step_time_ms": {"mean": 1000 * float(np.mean(step_times)) if step_times else None,
                              "p50": 1000 * float(np.percentile(step_times, 50)) if step_times else None,
                              "p90": 1000 * float(np.percentile(step_times, 90)) if step_times else None},
-            "dtype": self.compute_dtype, "data": "imagenet-tfrecord" if loader else "synthetic",
+            "dtype": self.compute_dtype, "data": self._data_label(loader),
             "input_decode_s": loader.decode_s if loader else None,
             "variable_update": p.variable_update, "hip_graph": ev.use_graph,
             "eval": {"top_1_accuracy": top1, "top_5_accuracy": top5, "examples": ex, "checkpoint_step": ckpt_step},
@@ -446,7 +499,7 @@ class BenchmarkCNN:
             # (graph-captured) input buffers by the native prefetch + GPU preprocess pipeline
             loader = self._loader(train=not p.forward_only)
             if self.rank == 0:
-                log_fn(f"Reading {len(loader.files)} TFRecord shards from {p.data_dir}")
+                log_fn(f"Reading {len(loader.files)} {self._files_word()} from {p.data_dir}")
         self.loader = loader
         # restore (rank 0) then broadcast_global_variables(0)
         if p.train_dir:
@@ -605,7 +658,7 @@ class BenchmarkCNN:
             "step_time_ms": {"mean": 1000 * float(np.mean(step_times)) if step_times else None,
                              "p50": 1000 * float(np.percentile(step_times, 50)) if step_times else None,
                              "p90": 1000 * float(np.percentile(step_times, 90)) if step_times else None},
-            "dtype": self.compute_dtype, "data": "imagenet-tfrecord" if loader else "synthetic",
+            "dtype": self.compute_dtype, "data": self._data_label(loader),
             "input_decode_s": loader.decode_s if loader else None,
             "variable_update": p.variable_update, "comm_engine": p.comm_engine if self.size > 1 else None,
             "gradient_compression": p.gradient_compression, "hip_graph": self.trainer.use_graph,

@@ -47,7 +47,7 @@ FLAGS: List[Flag] = [
     Flag("num_batches", None, int, "timed steps (default 100; with --eval on real data and neither this nor "
          "--num_epochs given: one pass over the validation split)"),
     Flag("model", "trivial", str, "model name: resnet50|101|152[_v1.5], inception3, mobilenet, vgg11|16|19, alexnet, googlenet, "
-         "overfeat, lenet, trivial"),
+         "overfeat, lenet, trivial; with --data_name=cifar10: resnet20|32|44|56|110, trivial"),
     Flag("num_intra_threads", 0, int, "host intra-op threads (CPU path: torch.set_num_threads)"),
     Flag("num_inter_threads", 0, int, "host inter-op threads (CPU path)"),
     Flag("kmp_blocktime", 0, int, "KMP_BLOCKTIME for the CPU path", noop_on_gpu=True),
@@ -75,8 +75,12 @@ FLAGS: List[Flag] = [
          choices=["horovod", "replicated", "parameter_server", "distributed_replicated", "independent"]),
     Flag("horovod_device", "", str, "where gradients are reduced: gpu (RCCL, default) | cpu (gloo)"),
     Flag("local_parameter_device", "gpu", str, "accepted for compatibility", noop_on_gpu=True),
-    Flag("data_dir", None, str, "real-data directory; absent = synthetic ImageNet"),
-    Flag("data_name", None, str, "dataset name (imagenet)"),
+    Flag("data_dir", None, str, "real-data directory: ImageNet TFRecord shards, or with --data_name=cifar10 the "
+         "python pickles (data_batch_1..5, test_batch; also looked for in its cifar-10-batches-py/); absent = "
+         "synthetic images of the dataset's size"),
+    Flag("data_name", None, str, "dataset: imagenet (default; 224 x 224, 1001 classes, 1,281,167 images per epoch) | "
+         "cifar10 (32 x 32, 11 classes, 50,000 images per epoch, held in device memory; models resnet20|32|44|56|110, "
+         "trivial)"),
     Flag("datasets_num_private_threads", None, int, "TFRecord reader threads per worker (real data)"),
     Flag("num_decode_threads", None, int, "JPEG decode threads per worker (real data)"),
     Flag("distortions", True, parse_bool, "real-data training preprocessing: true = random distorted crop + flip "
@@ -103,7 +107,7 @@ FLAGS: List[Flag] = [
     *[Flag(f"{opt}_{k}", v, float, f"{k} for --optimizer={opt}") for opt, args in OPT_DEFAULTS.items()
       for k, v in args.items()],
     Flag("weight_decay", 0.00004, float, "L2 weight decay (coupled, tf_cnn_benchmarks semantics)"),
-    Flag("num_epochs", None, float, "alternative to --num_batches"),
+    Flag("num_epochs", None, float, "alternative to --num_batches (epochs of the dataset: 1,281,167 images, cifar10 50,000)"),
     Flag("train_dir", None, str, "checkpoint directory"),
     Flag("save_model_steps", None, int, "checkpoint every N steps"),
     Flag("save_model_secs", 0, int, "checkpoint every N seconds"),
@@ -206,7 +210,8 @@ def noop_flags_set(p: Params) -> Dict[str, Any]:
 # (bf16x6 plane GEMMs, fp32 BN / pool / loss): their classes set F32_NATIVE_OK. Kept here, torch-free,
 # for the launcher's config echo; tests/test_cli.py checks it against the model classes.
 FP32_NATIVE_MODELS = frozenset({"resnet50", "resnet50_v1.5", "resnet101", "resnet101_v1.5", "resnet152",
-                                "resnet152_v1.5", "resnet50_v2", "resnet101_v2", "resnet152_v2", "inception3", "mobilenet", "vgg11", "vgg16", "vgg19", "alexnet", "overfeat",
+                                "resnet152_v1.5", "resnet50_v2", "resnet101_v2", "resnet152_v2", "resnet20", "resnet32", "resnet44",
+                                "resnet56", "resnet110", "inception3", "mobilenet", "vgg11", "vgg16", "vgg19", "alexnet", "overfeat",
                                 "lenet", "googlenet", "trivial"})
 
 

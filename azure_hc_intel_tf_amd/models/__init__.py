@@ -19,6 +19,19 @@ def _resnet_v2(depth):
     return make
 
 
+def _resnet_cifar(depth):
+    def make(**kw):
+        from .resnet_cifar import ResNetCifar
+
+        return ResNetCifar(depth=depth, **kw)
+
+    return make
+
+
+# the CIFAR-10 ResNets (32 x 32 input): built only with --data_name=cifar10
+CIFAR_MODELS = ("resnet20", "resnet32", "resnet44", "resnet56", "resnet110")
+
+
 def _inception3(**kw):
     from .inception import InceptionV3
 
@@ -56,6 +69,7 @@ _MODELS = {
     "resnet50_v2": _resnet_v2(50),
     "resnet101_v2": _resnet_v2(101),
     "resnet152_v2": _resnet_v2(152),
+    **{name: _resnet_cifar(int(name[len("resnet"):])) for name in CIFAR_MODELS},
     "inception3": _inception3,
     "mobilenet": _mobilenet,
     "trivial": _trivial,

@@ -856,6 +856,31 @@ class Dropout(Layer):
         self._mask = None
 
 
+class PadShortcut(Layer):
+    """The CIFAR ResNets' parameter-free ("plan A") shortcut: stride-``stride`` subsample, then a centred
+    zero pad of the channels to ``cout`` (tf_cnn_benchmarks: apool(1, 1, s, s) 'VALID' + tf.pad). The
+    forward writes the block input's format (16-bit, fp32, or Planes on the fp32 path), which is the
+    format the block output's BN pass reads its residual in; the backward writes the whole plain dx the
+    block's first data-gradient GEMM then accumulates into."""
+
+    def __init__(self, name, in_shape, cout: int, stride: int):
+        H, W, C = in_shape
+        assert cout >= C and (cout - C) % 2 == 0 and stride in (1, 2)
+        self.name = name
+        self.in_shape = in_shape
+        self.stride = stride
+        self.out_shape = (-(-H // stride), -(-W // stride), cout)
+
+    def forward(self, x):
+        shape = (x.shape[0],) + tuple(self.out_shape)
+        y = Fn.Planes.empty(shape, x.device) if Fn.is_planes(x) else torch.empty(shape, dtype=x.dtype, device=x.device)
+        return Fn.shortcut_pad_forward(x, y, self.stride)
+
+    def backward(self, g):
+        dx = empty_act((g.shape[0],) + tuple(self.in_shape), g.device)
+        return Fn.shortcut_pad_backward(g, dx, self.stride)
+
+
 class GlobalAvgPool(Layer):
     def __init__(self, name, in_shape):
         self.name = name

@@ -1423,6 +1423,38 @@ def gap_backward(dy, dx):
     return dx
 
 
+# --------------------------------------------------------------- plan-A shortcut
+def shortcut_pad_forward(x, out, s: int):
+    """The CIFAR ResNets' parameter-free shortcut (csrc/kernels/shortcut.hip): out[n, p, q, k] =
+    x[n, p*s, q*s, k - pad] for pad <= k < pad + C, else 0, with pad = (K - C) / 2 and out
+    [N, ceil(H/s), ceil(W/s), K] -- tf_cnn_benchmarks' apool(1, 1, s, s) 'VALID' + tf.pad on the
+    channels. A bit-exact copy in ``x``'s format: 16-bit, fp32, or Planes (``out`` Planes too; the
+    three planes go through one launch). The kernel writes every element of ``out``."""
+    C, K = x.shape[-1], out.shape[-1]
+    if native(x):
+        assert is_planes(x) == is_planes(out), "shortcut_pad_forward: out in x's format"
+        _ext.ops().shortcut_pad_fwd(_pl(x), _pl(out), s)
+        return out
+    pad = (K - C) // 2
+    assert K >= C and K - C == 2 * pad, "K - C must be even and >= 0"
+    out.copy_(F.pad(x[:, ::s, ::s], (pad, pad)))
+    return out
+
+
+def shortcut_pad_backward(g, dx, s: int):
+    """The adjoint: dx[n, h, w, c] = g[n, h/s, w/s, pad + c] where h % s == 0 and w % s == 0, else 0.
+    ``g`` and ``dx`` are plain activations (16-bit or fp32); every element of ``dx`` is written by the
+    kernel (no zero-fill launch: the captured step stays free of memset nodes)."""
+    C, K = dx.shape[-1], g.shape[-1]
+    if native(g):
+        _ext.ops().shortcut_pad_bwd(g, dx, s)
+        return dx
+    pad = (K - C) // 2
+    dx.zero_()
+    dx[:, ::s, ::s] = g[..., pad:pad + C]
+    return dx
+
+
 # ------------------------------------------------------------------------- loss
 def softmax_xent(logits, labels, ncls, row_loss, dlogits, scale, scale_dev=None, dl32=None,
                  label_smoothing: float = 0.0):

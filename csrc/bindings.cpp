@@ -1211,6 +1211,102 @@ void preprocess_distort(const Tensor& src, const Tensor& desc, const Tensor& des
                                  bi, f32, cur_stream());
 }
 
+// CIFAR-10 batch from the device-resident split (kernels/cifar.hip). desc [B][4] int32 = (index | -1, oy,
+// ox, flip); desc_host: its CPU copy, every row range-checked here before anything is launched
+void cifar_batch(const Tensor& data, const Tensor& labels_all, const Tensor& desc, const Tensor& desc_host,
+                 const Tensor& out, const Tensor& labels_out) {
+  check_cuda(data, "data");
+  check_cuda(labels_all, "labels_all");
+  check_cuda(desc, "desc");
+  check_cuda(labels_out, "labels_out");
+  const bool f32 = check_act_or_f32(out, "out");
+  TORCH_CHECK(data.scalar_type() == at::kByte && data.is_contiguous() && data.dim() == 4 && data.size(1) == 3 &&
+                  data.size(2) == 32 && data.size(3) == 32,
+              "hcb.cifar_batch: data uint8 [N][3][32][32] contiguous");
+  const int64_t N = data.size(0);
+  TORCH_CHECK(N * 3072 < (1ll << 40), "hcb.cifar_batch: dataset too large");
+  TORCH_CHECK(labels_all.scalar_type() == at::kLong && labels_all.is_contiguous() && labels_all.dim() == 1 &&
+                  labels_all.size(0) == N,
+              "hcb.cifar_batch: labels_all int64 [N] contiguous");
+  TORCH_CHECK(desc.scalar_type() == at::kInt && desc.dim() == 2 && desc.size(1) == 4 && desc.is_contiguous(),
+              "hcb.cifar_batch: desc int32 [B][4]");
+  TORCH_CHECK(!desc_host.is_cuda() && desc_host.scalar_type() == at::kInt && desc_host.is_contiguous() &&
+                  desc_host.sizes() == desc.sizes(),
+              "hcb.cifar_batch: desc_host must be the CPU copy of desc");
+  const int64_t B = desc.size(0);
+  TORCH_CHECK(out.dim() == 4 && out.is_contiguous() && out.size(0) == B && out.size(1) == 32 && out.size(2) == 32 &&
+                  out.size(3) % 8 == 0 && out.size(3) >= 8,
+              "hcb.cifar_batch: out [B][32][32][Cpad] contiguous, Cpad % 8 == 0");
+  TORCH_CHECK(labels_out.scalar_type() == at::kLong && labels_out.is_contiguous() && labels_out.dim() == 1 &&
+                  labels_out.size(0) == B,
+              "hcb.cifar_batch: labels_out int64 [B] contiguous");
+  TORCH_CHECK(data.device() == out.device() && labels_all.device() == out.device() && desc.device() == out.device() &&
+                  labels_out.device() == out.device(),
+              "hcb.cifar_batch: data, labels_all, desc, out and labels_out on one device");
+  TORCH_CHECK(B < 65536, "hcb.cifar_batch: batch too large");
+  check_align16(out.data_ptr(), "out");
+  const int* d = desc_host.data_ptr<int>();
+  for (int64_t i = 0; i < B; ++i) {
+    TORCH_CHECK(d[4 * i] >= -1 && d[4 * i] < N, "hcb.cifar_batch: index of row ", i, " outside [-1, N)");
+    TORCH_CHECK(d[4 * i + 1] >= 0 && d[4 * i + 1] <= 8 && d[4 * i + 2] >= 0 && d[4 * i + 2] <= 8,
+                "hcb.cifar_batch: crop offset of row ", i, " outside [0, 8]");
+    TORCH_CHECK(d[4 * i + 3] == 0 || d[4 * i + 3] == 1, "hcb.cifar_batch: flip of row ", i, " must be 0 or 1");
+  }
+  if (B == 0) return;
+  hcb::launch_cifar_batch(data.data_ptr<uint8_t>(), labels_all.data_ptr<int64_t>(), desc.data_ptr<int>(), (int)B,
+                          out.data_ptr(), labels_out.data_ptr<int64_t>(), (int)out.size(3), f32, cur_stream());
+}
+
+// Plan-A shortcut (kernels/shortcut.hip): the geometry of x [N][H][W][C] (or its planes [3][N][H][W][C]) against
+// y [N][P][Q][K] at stride s, in 16-byte vectors; refuses what the kernels do not do, by name
+struct ShortcutGeom {
+  int64_t NI;
+  int H, W, P, Q, s, Cv, Kv, padv;
+};
+ShortcutGeom shortcut_geom(const Tensor& x, const Tensor& y, int64_t s, const char* op) {
+  check_cuda(x, "x");
+  check_cuda(y, "y");
+  TORCH_CHECK(x.device() == y.device(), "hcb.", op, ": both tensors on one device");
+  const auto dt = x.scalar_type();
+  TORCH_CHECK(dt == y.scalar_type() && (dt == kAct || dt == at::kFloat || dt == at::kBFloat16),
+              "hcb.", op, ": both tensors " HCB_ACT_NAME ", float32 or bfloat16 planes, of one dtype");
+  TORCH_CHECK(x.dim() == y.dim() && (x.dim() == 4 || (x.dim() == 5 && dt == at::kBFloat16 && x.size(0) == 3)),
+              "hcb.", op, ": [N][H][W][C] tensors, or bf16 planes [3][N][H][W][C]");
+  TORCH_CHECK(x.is_contiguous() && y.is_contiguous(), "hcb.", op, ": contiguous tensors only");
+  const int o = x.dim() - 4;
+  TORCH_CHECK(y.size(0) == x.size(0) && y.size(o) == x.size(o), "hcb.", op, ": batch sizes differ");
+  TORCH_CHECK(s == 1 || s == 2, "hcb.", op, ": stride 1 or 2");
+  const int64_t H = x.size(o + 1), W = x.size(o + 2), C = x.size(o + 3);
+  const int64_t P = y.size(o + 1), Q = y.size(o + 2), K = y.size(o + 3);
+  TORCH_CHECK(H > 0 && W > 0 && H < (1 << 20) && W < (1 << 20), "hcb.", op, ": bad spatial size");
+  TORCH_CHECK(P == (H + s - 1) / s && Q == (W + s - 1) / s, "hcb.", op, ": output is [ceil(H / s)][ceil(W / s)]");
+  TORCH_CHECK(K >= C && (K - C) % 2 == 0, "hcb.", op, ": K - C must be even and >= 0 (a centred channel pad)");
+  TORCH_CHECK(C % 8 == 0 && C > 0 && ((K - C) / 2) % 8 == 0, "hcb.", op,
+              ": C % 8 == 0 and pad % 8 == 0 (pad = (K - C) / 2) only");
+  const int64_t e = (int64_t)x.element_size();
+  ShortcutGeom g;
+  g.NI = x.numel() / (H * W * C);
+  g.H = (int)H, g.W = (int)W, g.P = (int)P, g.Q = (int)Q, g.s = (int)s;
+  g.Cv = (int)(C * e / 16), g.Kv = (int)(K * e / 16), g.padv = (int)((K - C) / 2 * e / 16);
+  TORCH_CHECK((y.numel() * e / 16 + 255) / 256 < (1ll << 31) && (x.numel() * e / 16 + 255) / 256 < (1ll << 31),
+              "hcb.", op, ": tensor too large");
+  check_align16(x.data_ptr(), "x");
+  check_align16(y.data_ptr(), "y");
+  return g;
+}
+
+void shortcut_pad_fwd(const Tensor& x, const Tensor& y, int64_t s) {
+  const ShortcutGeom g = shortcut_geom(x, y, s, "shortcut_pad_fwd");
+  hcb::launch_shortcut_pad_fwd(x.data_ptr(), y.data_ptr(), g.NI, g.H, g.W, g.P, g.Q, g.s, g.Cv, g.Kv, g.padv, cur_stream());
+}
+
+// dx [N][H][W][C] = the adjoint applied to g [N][P][Q][K]: every element of dx is written
+void shortcut_pad_bwd(const Tensor& g, const Tensor& dx, int64_t s) {
+  TORCH_CHECK(g.dim() == 4, "hcb.shortcut_pad_bwd: the gradient is a plain [N][P][Q][K] activation");
+  const ShortcutGeom q = shortcut_geom(dx, g, s, "shortcut_pad_bwd");
+  hcb::launch_shortcut_pad_bwd(g.data_ptr(), dx.data_ptr(), q.NI, q.H, q.W, q.P, q.Q, q.s, q.Cv, q.Kv, q.padv, cur_stream());
+}
+
 static int pack_mode(const Tensor& t, const char* what) {
   switch (t.scalar_type()) {
     case at::kFloat: return 0;
@@ -1519,6 +1615,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("preprocess_images(Tensor src, Tensor desc, Tensor desc_host, Tensor(a!) out, float[] scale, float[] bias) -> ()");
   m.def("preprocess_distort(Tensor src, Tensor desc, Tensor desc_host, Tensor params, Tensor params_host, "
         "Tensor(a!) out, Tensor(b!) work, float[] scale, float[] bias) -> ()");
+  m.def("cifar_batch(Tensor data, Tensor labels_all, Tensor desc, Tensor desc_host, Tensor(a!) out, Tensor(b!) labels_out) -> ()");
+  m.def("shortcut_pad_fwd(Tensor x, Tensor(a!) y, int s) -> ()");
+  m.def("shortcut_pad_bwd(Tensor g, Tensor(a!) dx, int s) -> ()");
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
         "Tensor(e!) run_mean, Tensor(f!) run_var, Tensor? shift=None) -> ()");
@@ -1583,6 +1682,9 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("dropout_bwd", dropout_bwd);
   m.impl("preprocess_images", preprocess_images);
   m.impl("preprocess_distort", preprocess_distort);
+  m.impl("cifar_batch", cifar_batch);
+  m.impl("shortcut_pad_fwd", shortcut_pad_fwd);
+  m.impl("shortcut_pad_bwd", shortcut_pad_bwd);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);

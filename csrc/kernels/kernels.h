@@ -301,6 +301,19 @@ void launch_preprocess_distort(const uint8_t* src, const int64_t* desc, const fl
                                void* out, float* work, int S, int Cpad, const float* scale, const float* bias,
                                bool f32, hipStream_t st);
 
+// CIFAR-10 (cifar.hip): data uint8 [N][3][32][32] resident on the device, desc [B][4] int32 = (index | -1,
+// oy, ox, flip) -> out [B][32][32][Cpad] (pad 4, crop at (oy, ox), flip, x/127.5 - 1) and labels_out [B]
+void launch_cifar_batch(const uint8_t* data, const int64_t* labels_all, const int* desc, int B, void* out,
+                        int64_t* labels_out, int Cpad, bool f32, hipStream_t st);
+
+// ---------------------------------------------------------------- plan-A shortcut (shortcut.hip)
+// stride-s subsample + centred zero pad of the channels and its gradient, in 16-byte vectors: x / dx
+// [NI][H][W][Cv], y / g [NI][P][Q][Kv], Kv == Cv + 2 * padv, P == ceil(H / s), Q == ceil(W / s)
+void launch_shortcut_pad_fwd(const void* x, void* y, int64_t NI, int H, int W, int P, int Q, int s, int Cv, int Kv,
+                             int padv, hipStream_t st);
+void launch_shortcut_pad_bwd(const void* g, void* dx, int64_t NI, int H, int W, int P, int Q, int s, int Cv, int Kv,
+                             int padv, hipStream_t st);
+
 // ---------------------------------------------------------------- space-to-depth stem (stem.hip)
 void launch_stem_s2d_f32(const float* x, int N, int H, int W, int ldx, uint16_t* out, int64_t plane, int Hs, int Ws,
                          int pad, hipStream_t st);
