@@ -49,6 +49,8 @@ def check_dataset(p: Params) -> str:
             raise ValueError("--color_distortions is an ImageNet preprocessing step: not with --data_name=cifar10")
         if p.resize_method != "bilinear":
             raise ValueError("--resize_method: CIFAR-10 images are never resized (not with --data_name=cifar10)")
+        if p.gpu_jpeg_decode:
+            raise ValueError("--gpu_jpeg_decode decodes ImageNet JPEGs: CIFAR-10 has none (not with --data_name=cifar10)")
         if p.image_size and p.image_size != 32:
             raise ValueError("--data_name=cifar10 images are 32 x 32: --image_size must be 32 or absent")
     elif p.model in CIFAR_MODELS:
@@ -240,6 +242,11 @@ class BenchmarkCNN:
         elif p.data_dir and not p.eval and not p.forward_only:
             log_fn("Distortions: " + (f"crop+flip{'+color' if p.color_distortions else ''}, resize={p.resize_method}"
                                       if p.distortions else "none (central crop), resize=bilinear"))
+        if p.gpu_jpeg_decode:
+            log_fn("JPEG decode: " + ("host Huffman stage + jpeg_idct / jpeg_crop_rgb " +
+                                      ("HIP kernels" if self.on_gpu else "reference (CPU)") +
+                                      "; declined images: Pillow" if p.data_dir else
+                                      "--gpu_jpeg_decode ignored: synthetic data has no JPEGs (no --data_dir)"))
         log_fn(f"SingleSess:  False")
         log_fn(f"Batch size:  {self.batch_size * self.size} global")
         log_fn(f"             {self.batch_size} per device")
@@ -285,7 +292,19 @@ class BenchmarkCNN:
                               self.device, rank=self.rank, world=self.size, train=train, loop=loop,
                               seed=p.tf_random_seed, reader_threads=p.datasets_num_private_threads or 4,
                               decode_threads=p.num_decode_threads or 8, distort=p.distortions,
-                              color=p.color_distortions, resize_method=p.resize_method)
+                              color=p.color_distortions, resize_method=p.resize_method,
+                              gpu_decode=bool(p.gpu_jpeg_decode))
+
+    def _jpeg_counts(self, loader):
+        """--gpu_jpeg_decode: images the GPU path decoded against images it declined to Pillow (this rank),
+        logged and returned for the JSON summary; None without the flag."""
+        if loader is None or not getattr(loader, "gpu_decode", False):
+            return None
+        counts = {"gpu": int(loader.gpu_decoded), "declined": int(loader.gpu_declined),
+                  "reasons": dict(loader.decline_reasons)}
+        log_fn(f"JPEG decode: {counts['gpu']} images on the GPU path, {counts['declined']} declined to Pillow"
+               + (f" {counts['reasons']}" if counts["reasons"] else ""))
+        return counts
 
     def _files_word(self) -> str:
         return "CIFAR-10 pickles" if self.data_name == "cifar10" else "TFRecord shards"
@@ -463,7 +482,7 @@ class BenchmarkCNN:
                              "p50": 1000 * float(np.percentile(step_times, 50)) if step_times else None,
                              "p90": 1000 * float(np.percentile(step_times, 90)) if step_times else None},
             "dtype": self.compute_dtype, "data": self._data_label(loader),
-            "input_decode_s": loader.decode_s if loader else None,
+            "input_decode_s": loader.decode_s if loader else None, "jpeg_decode": self._jpeg_counts(loader),
             "variable_update": p.variable_update, "hip_graph": ev.use_graph,
             "eval": {"top_1_accuracy": top1, "top_5_accuracy": top5, "examples": ex, "checkpoint_step": ckpt_step},
         }
@@ -659,7 +678,7 @@ class BenchmarkCNN:
                              "p50": 1000 * float(np.percentile(step_times, 50)) if step_times else None,
                              "p90": 1000 * float(np.percentile(step_times, 90)) if step_times else None},
             "dtype": self.compute_dtype, "data": self._data_label(loader),
-            "input_decode_s": loader.decode_s if loader else None,
+            "input_decode_s": loader.decode_s if loader else None, "jpeg_decode": self._jpeg_counts(loader),
             "variable_update": p.variable_update, "comm_engine": p.comm_engine if self.size > 1 else None,
             "gradient_compression": p.gradient_compression, "hip_graph": self.trainer.use_graph,
             "fusion_threshold_bytes": getattr(self.reducer, "bucket_bytes", None),

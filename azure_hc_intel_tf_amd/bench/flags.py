@@ -136,6 +136,10 @@ FLAGS: List[Flag] = [
     Flag("color_distortions", False, parse_bool, "with --distortions: also tf_cnn_benchmarks' distort_color (random "
          "brightness, saturation, hue, contrast; the preprocess_distort HIP kernels). Upstream's --distortions=true "
          "is --distortions=true --color_distortions=true here"),
+    Flag("gpu_jpeg_decode", False, parse_bool, "real ImageNet data: decode JPEGs with the host Huffman stage "
+         "(csrc/data/jpeg.cpp) and the jpeg_idct / jpeg_crop_rgb HIP kernels instead of Pillow; images the native "
+         "decoder declines (progressive, CMYK, PNG, over the coefficient budget, ...) still go through Pillow. "
+         "Ignored without --data_dir, refused with --data_name=cifar10"),
     Flag("json_summary", None, str, "write the run summary JSON to this path"),
     Flag("comm_profile", True, parse_bool, "after the timed run (N>1, GPU): measure allreduce time, exposed "
          "communication and overlap % for the JSON summary"),

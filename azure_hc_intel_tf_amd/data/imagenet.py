@@ -39,6 +39,19 @@ weights from the exact fraction, not TF's 1024-entry weight table (parity unpinn
 (crop + flip, no colour, bilinear) keep the ``preprocess_images`` kernel; anything else runs
 ``preprocess_distort`` (csrc/kernels/distort.hip) on the GPU and ``preprocess_distort_reference``,
 the definition of both, on ``--device=cpu``.
+
+GPU JPEG decode (``gpu_decode=True``, ``--gpu_jpeg_decode``; data/jpeg.py). The decode pool calls the
+native entropy decoder (csrc/data/jpeg.cpp, GIL released) once per sample with the destination inside
+the pinned slot: image i of a batch owns ``coef_budget(max_side)`` bytes there, 3 bytes per source pixel
+of a max_side x max_side window (about 2.4 MB at 224 px), and an image whose window needs more is
+declined. The records go to the device one copy per image, ``jpeg_idct`` and ``jpeg_crop_rgb`` write the
+RGB crops into ``dev_stage`` under the usual (offset, h, w, flip) rows, and the preprocess kernels run
+unchanged. Declined images (progressive, CMYK, PNG, damaged, over budget, reduced crop over max_side)
+are decoded by ``decode_crop`` and uploaded into ``dev_stage`` behind the kernel-written crops, so a
+batch may mix both; ``gpu_decoded`` / ``gpu_declined`` / ``decline_reasons`` count them. Crop windows,
+flips, labels, shuffle order and distortion draws do not depend on the flag; the reduced crop is
+(h // r, w // r) by the r x r box mean instead of Pillow's DCT-domain draft. On ``--device=cpu``
+``jpeg_decode_reference`` runs in place of the kernels.
 """
 from __future__ import annotations
 
@@ -51,6 +64,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import jpeg as _jpeg
 from .tfrecord import find_shards, native
 
 SCALE = (1.0 / 127.5,) * 3
@@ -272,7 +286,8 @@ class ImageNetLoader:
     def __init__(self, data_dir: str, batch_size: int, image_size: int, channels: int, device,
                  rank: int = 0, world: int = 1, train: bool = True, seed: int = 0, reader_threads: int = 4,
                  decode_threads: int = 8, depth: int = 3, shuffle_buffer: int = 4096, subset: Optional[str] = None,
-                 loop: bool = True, distort: bool = True, color: bool = False, resize_method: str = "bilinear"):
+                 loop: bool = True, distort: bool = True, color: bool = False, resize_method: str = "bilinear",
+                 gpu_decode: bool = False):
         self.B = batch_size
         # distort / color / resize_method: see the module docstring; evaluation loaders ignore them
         if resize_method != "round_robin" and resize_method not in RESIZE_METHODS:
@@ -315,6 +330,23 @@ class ImageNetLoader:
             self.dev_params = torch.empty((batch_size, 8), dtype=torch.float32, device=self.device)
             self.dev_work = torch.empty(distort_work_numel(batch_size, image_size), dtype=torch.float32,
                                         device=self.device)
+        # gpu_decode: every slot grows by one entropy-decoder record of coef_budget bytes per image, in
+        # front of the RGB area that now only holds the crops of declined images
+        self.gpu_decode = bool(gpu_decode)
+        self.gpu_decoded = 0
+        self.gpu_declined = 0
+        self.decline_reasons: dict = {}
+        self._gpu_info = [None] * depth  # per slot: the kernels' tables and copies of the batch it holds
+        if self.gpu_decode:
+            self.budget = _jpeg.coef_budget(self.max_side)
+            self.coef_slots = [torch.empty(batch_size * self.budget, dtype=torch.uint8, pin_memory=pin)
+                               for _ in range(depth)]
+            if pin:
+                self.dev_coef = torch.empty(batch_size * self.budget, dtype=torch.uint8, device=self.device)
+                # one byte of plane per int16 coefficient
+                self.dev_planes = torch.empty(batch_size * (self.budget // 2), dtype=torch.uint8, device=self.device)
+                self.dev_segs = torch.empty((3 * batch_size, _jpeg.SEG_COLS), dtype=torch.int64, device=self.device)
+                self.dev_imgs = torch.empty((batch_size, _jpeg.IMG_COLS), dtype=torch.int64, device=self.device)
         self.free: "queue.Queue" = queue.Queue()
         for i in range(depth):
             self.free.put((i, None))
@@ -362,6 +394,11 @@ class ImageNetLoader:
                     if real == 0:  # one pass done: the consumer returns 0 from here on
                         self.ready.put(_END)
                         return
+                if self.gpu_decode:
+                    item = self._produce_gpu_decode(slot, samples, real)
+                    self.decode_s += time.perf_counter() - t0
+                    self.ready.put(item)
+                    continue
                 crops = list(self.pool.map(
                     lambda s: decode_crop(s[0], s[2], s[4], self.S, self.max_side), samples))
                 buf = self.slots[slot].numpy()
@@ -383,6 +420,66 @@ class ImageNetLoader:
             self._err = e
             self.ready.put(None)
 
+    def _produce_gpu_decode(self, slot: int, samples, real: int):
+        """One batch with gpu_decode: entropy-decode every sample into its record of the slot (decode
+        pool), fall back to decode_crop per declined image, lay out the stage (GPU crops first, in batch
+        order, then the fallback crops) and build the kernels' tables. Descriptor order is batch order."""
+        nat = native()
+        cbuf = self.coef_slots[slot].numpy()
+        budget = self.budget
+        on_gpu = self.device.type == "cuda"
+
+        def work(i):
+            s = samples[i]
+            res = nat.jpeg_entropy_decode(s[0], s[2], cbuf[i * budget:(i + 1) * budget])
+            if isinstance(res, str):
+                return res, None, decode_crop(s[0], s[2], s[4], self.S, self.max_side)
+            hdr, qt, coef = _jpeg.parse_record(cbuf[i * budget:i * budget + res])
+            r = _jpeg.reduction(hdr["ch"], hdr["cw"], self.S)
+            if max(hdr["ch"] // r, hdr["cw"] // r) > self.max_side:
+                return "declined: reduced crop over max_side", None, decode_crop(s[0], s[2], s[4], self.S, self.max_side)
+            if not on_gpu:  # the definition is the CPU path
+                return None, (hdr, r), _jpeg.jpeg_decode_reference(coef, hdr, qt, r)
+            return None, (hdr, r), None
+
+        res = list(self.pool.map(work, range(real)))
+        desc = np.zeros((self.B, 4), dtype=np.int64)
+        headers, rs, crops = [None] * self.B, [1] * self.B, [None] * self.B
+        off = 0
+        for i, (why, hr, crop) in enumerate(res):  # kernel-written crops first
+            if why is not None:
+                self.gpu_declined += 1
+                self.decline_reasons[why[len("declined: "):]] = self.decline_reasons.get(why[len("declined: "):], 0) + 1
+                continue
+            self.gpu_decoded += 1
+            headers[i], rs[i] = hr
+            oh, ow = hr[0]["ch"] // hr[1], hr[0]["cw"] // hr[1]
+            desc[i] = (off, oh, ow, samples[i][3])
+            crops[i] = crop
+            off += (oh * ow * 3 + 15) // 16 * 16
+        gpu_bytes = off
+        buf = self.slots[slot].numpy()
+        for i, (why, hr, crop) in enumerate(res):  # then the Pillow-decoded ones, packed from the slot's start
+            if why is None:
+                continue
+            n = crop.size
+            buf[off - gpu_bytes:off - gpu_bytes + n] = crop.reshape(-1)
+            desc[i] = (off, crop.shape[0], crop.shape[1], samples[i][3])
+            crops[i] = crop
+            off += (n + 15) // 16 * 16
+        desc[real:] = desc[0]  # padding rows of a short last batch: the first image again (no second decode)
+        crops[real:] = [crops[0]] * (self.B - real)
+        labels = np.full(self.B, -1, dtype=np.int64)
+        labels[:real] = [s[1] for s in samples]
+        prm = self._draw_params() if self.distort_op else None
+        gpu = None
+        if on_gpu:
+            segs, imgs, plane_bytes, _ = _jpeg.build_tables(headers, [i * budget for i in range(self.B)], rs)
+            copies = [(i * budget, headers[i]["nbytes"]) for i in range(self.B) if headers[i] is not None]
+            gpu = (segs, imgs, copies, gpu_bytes, off - gpu_bytes)
+        self._gpu_info[slot] = gpu  # the slot is the producer's until the item is taken, then the consumer's
+        return slot, desc, labels, None if on_gpu else crops, real, prm
+
     # ---------------------------------------------------------------- consumer
     def next_into(self, images: torch.Tensor, labels: torch.Tensor) -> int:
         """Write the next batch into ``images`` [B, S, S, C] / ``labels`` [B] in place (stream
@@ -398,13 +495,29 @@ class ImageNetLoader:
             self._exhausted = True
             return 0
         slot, desc, lab, crops, real, prm = item
+        gpu = self._gpu_info[slot] if self.gpu_decode else None
         if self.device.type == "cuda":
-            nbytes = int(desc[real - 1, 0] + desc[real - 1, 1] * desc[real - 1, 2] * 3)
-            self.dev_stage[:nbytes].copy_(self.slots[slot][:nbytes], non_blocking=True)
+            from ..ops import _ext
+
             desc_t = torch.from_numpy(desc)
             self.dev_desc.copy_(desc_t, non_blocking=True)
             labels.copy_(torch.from_numpy(lab), non_blocking=True)
-            from ..ops import _ext
+            if gpu is None:
+                nbytes = int(desc[real - 1, 0] + desc[real - 1, 1] * desc[real - 1, 2] * 3)
+                self.dev_stage[:nbytes].copy_(self.slots[slot][:nbytes], non_blocking=True)
+            else:
+                segs, imgs, copies, gpu_bytes, fb_bytes = gpu
+                for o, n in copies:  # one record per GPU-decoded image
+                    self.dev_coef[o:o + n].copy_(self.coef_slots[slot][o:o + n], non_blocking=True)
+                if fb_bytes:  # the Pillow-decoded crops, behind the kernel-written ones
+                    self.dev_stage[gpu_bytes:gpu_bytes + fb_bytes].copy_(self.slots[slot][:fb_bytes], non_blocking=True)
+                if len(copies):
+                    segs_t, imgs_t = torch.from_numpy(segs), torch.from_numpy(imgs)
+                    dev_segs = self.dev_segs[:segs.shape[0]]
+                    dev_segs.copy_(segs_t, non_blocking=True)
+                    self.dev_imgs.copy_(imgs_t, non_blocking=True)
+                    _ext.ops().jpeg_idct(self.dev_coef, dev_segs, segs_t, self.dev_planes)
+                    _ext.ops().jpeg_crop_rgb(self.dev_planes, self.dev_imgs, imgs_t, self.dev_desc, desc_t, self.dev_stage)
 
             if prm is None:
                 _ext.ops().preprocess_images(self.dev_stage, self.dev_desc, desc_t, images, list(SCALE), list(BIAS))

@@ -1257,6 +1257,122 @@ void cifar_batch(const Tensor& data, const Tensor& labels_all, const Tensor& des
                           out.data_ptr(), labels_out.data_ptr<int64_t>(), (int)out.size(3), f32, cur_stream());
 }
 
+// GPU JPEG decode, stage 1 (kernels/jpeg.hip): dequantise + 8x8 inverse DCT of every block of every image
+// component in one launch. coef: the records jpeg_entropy_decode wrote (csrc/data/jpeg.h); segs [nseg][8] =
+// (group0, nblocks, coefficient byte offset, record byte offset, quantisation table, plane byte offset, 0,
+// 0); segs_host: its CPU copy, every row range-checked here before anything is launched
+void jpeg_idct(const Tensor& coef, const Tensor& segs, const Tensor& segs_host, const Tensor& planes) {
+  check_cuda(coef, "coef");
+  check_cuda(segs, "segs");
+  check_cuda(planes, "planes");
+  TORCH_CHECK(coef.scalar_type() == at::kByte && coef.is_contiguous(), "hcb.jpeg_idct: coef uint8 contiguous");
+  TORCH_CHECK(planes.scalar_type() == at::kByte && planes.is_contiguous(), "hcb.jpeg_idct: planes uint8 contiguous");
+  TORCH_CHECK(segs.scalar_type() == at::kLong && segs.dim() == 2 && segs.size(1) == 8 && segs.is_contiguous(),
+              "hcb.jpeg_idct: segs int64 [nseg][8]");
+  TORCH_CHECK(!segs_host.is_cuda() && segs_host.scalar_type() == at::kLong && segs_host.is_contiguous() &&
+                  segs_host.sizes() == segs.sizes(),
+              "hcb.jpeg_idct: segs_host must be the CPU copy of segs");
+  TORCH_CHECK(coef.device() == segs.device() && planes.device() == segs.device(),
+              "hcb.jpeg_idct: coef, segs and planes on one device");
+  check_align16(coef.data_ptr(), "coef");
+  check_align16(planes.data_ptr(), "planes");
+  const int64_t nseg = segs.size(0), G = hcb::jpeg_idct_group_blocks();
+  TORCH_CHECK(nseg < (1ll << 24), "hcb.jpeg_idct: too many segments");
+  const int64_t* s = segs_host.data_ptr<int64_t>();
+  int64_t group = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const int64_t* r = s + 8 * i;
+    TORCH_CHECK(r[1] > 0 && r[1] < (1ll << 31), "hcb.jpeg_idct: block count of segment ", i, " out of range");
+    TORCH_CHECK(r[0] == group, "hcb.jpeg_idct: group prefix of segment ", i, " is ", r[0], ", expected ", group);
+    TORCH_CHECK(r[2] >= 0 && r[2] % 16 == 0 && r[2] + r[1] * 128 <= coef.numel(),
+                "hcb.jpeg_idct: coefficients of segment ", i, " outside coef (or not 16-byte aligned)");
+    TORCH_CHECK(r[4] >= 0 && r[4] <= 3, "hcb.jpeg_idct: quantisation table index of segment ", i, " outside [0, 3]");
+    TORCH_CHECK(r[3] >= 0 && r[3] % 16 == 0 && r[3] + 128 + 4 * 128 <= coef.numel(),
+                "hcb.jpeg_idct: record of segment ", i, " outside coef (or not 16-byte aligned)");
+    TORCH_CHECK(r[5] >= 0 && r[5] % 8 == 0 && r[5] + r[1] * 64 <= planes.numel(),
+                "hcb.jpeg_idct: plane of segment ", i, " outside planes (or not 8-byte aligned)");
+    TORCH_CHECK(r[6] == 0 && r[7] == 0, "hcb.jpeg_idct: the spare slots of segment ", i, " must be 0");
+    group += (r[1] + G - 1) / G;
+  }
+  TORCH_CHECK(group < (1ll << 31), "hcb.jpeg_idct: too many blocks");
+  if (nseg == 0) return;
+  hcb::launch_jpeg_idct(segs.data_ptr<int64_t>(), (int)nseg, group, coef.data_ptr<uint8_t>(), planes.data_ptr<uint8_t>(),
+                        cur_stream());
+}
+
+// GPU JPEG decode, stage 2 (kernels/jpeg.hip): chroma upsampling, YCbCr -> RGB, r x r box mean and crop, one
+// thread per pixel of the packed crops in stage. imgs [B][24] = (ncomp | 0 = row skipped, r, hs, vs, H, W, y0,
+// x0, 3 x (plane byte offset, bx0, by0, bw, bh), 0); desc [B][4] = (offset, h, w, flip) as preprocess_images
+// reads it afterwards; imgs_host / desc_host: the CPU copies, every window range-checked here before launch
+void jpeg_crop_rgb(const Tensor& planes, const Tensor& imgs, const Tensor& imgs_host, const Tensor& desc,
+                   const Tensor& desc_host, const Tensor& stage) {
+  check_cuda(planes, "planes");
+  check_cuda(imgs, "imgs");
+  check_cuda(desc, "desc");
+  check_cuda(stage, "stage");
+  TORCH_CHECK(planes.scalar_type() == at::kByte && planes.is_contiguous(), "hcb.jpeg_crop_rgb: planes uint8 contiguous");
+  TORCH_CHECK(stage.scalar_type() == at::kByte && stage.is_contiguous(), "hcb.jpeg_crop_rgb: stage uint8 contiguous");
+  TORCH_CHECK(imgs.scalar_type() == at::kLong && imgs.dim() == 2 && imgs.size(1) == 24 && imgs.is_contiguous(),
+              "hcb.jpeg_crop_rgb: imgs int64 [B][24]");
+  TORCH_CHECK(!imgs_host.is_cuda() && imgs_host.scalar_type() == at::kLong && imgs_host.is_contiguous() &&
+                  imgs_host.sizes() == imgs.sizes(),
+              "hcb.jpeg_crop_rgb: imgs_host must be the CPU copy of imgs");
+  const int64_t B = imgs.size(0);
+  TORCH_CHECK(desc.scalar_type() == at::kLong && desc.dim() == 2 && desc.size(0) == B && desc.size(1) == 4 &&
+                  desc.is_contiguous(),
+              "hcb.jpeg_crop_rgb: desc int64 [B][4]");
+  TORCH_CHECK(!desc_host.is_cuda() && desc_host.scalar_type() == at::kLong && desc_host.is_contiguous() &&
+                  desc_host.sizes() == desc.sizes(),
+              "hcb.jpeg_crop_rgb: desc_host must be the CPU copy of desc");
+  TORCH_CHECK(planes.device() == imgs.device() && desc.device() == imgs.device() && stage.device() == imgs.device(),
+              "hcb.jpeg_crop_rgb: planes, imgs, desc and stage on one device");
+  TORCH_CHECK(B < 65536, "hcb.jpeg_crop_rgb: batch too large");
+  const int64_t* t = imgs_host.data_ptr<int64_t>();
+  const int64_t* d = desc_host.data_ptr<int64_t>();
+  int64_t max_pixels = 0;
+  for (int64_t i = 0; i < B; ++i) {
+    const int64_t* r = t + 24 * i;
+    if (r[0] == 0) continue;
+    const int64_t ncomp = r[0], red = r[1], hs = r[2], vs = r[3], H = r[4], W = r[5], y0 = r[6], x0 = r[7];
+    const int64_t oh = d[4 * i + 1], ow = d[4 * i + 2];
+    TORCH_CHECK(ncomp == 1 || ncomp == 3, "hcb.jpeg_crop_rgb: component count of image ", i, " must be 0, 1 or 3");
+    TORCH_CHECK(red == 1 || red == 2 || red == 4 || red == 8, "hcb.jpeg_crop_rgb: reduction of image ", i,
+                " must be 1, 2, 4 or 8");
+    TORCH_CHECK((hs == 1 || hs == 2) && (vs == 1 || vs == 2) && (ncomp == 3 || (hs == 1 && vs == 1)),
+                "hcb.jpeg_crop_rgb: sampling factors of image ", i, " must be 1 or 2 (1 for a grey image)");
+    TORCH_CHECK(H > 0 && W > 0 && H <= 65535 && W <= 65535, "hcb.jpeg_crop_rgb: size of image ", i, " out of range");
+    TORCH_CHECK(oh > 0 && ow > 0 && y0 >= 0 && x0 >= 0 && y0 + oh * red <= H && x0 + ow * red <= W,
+                "hcb.jpeg_crop_rgb: crop window of image ", i, " outside the image");
+    TORCH_CHECK(d[4 * i] >= 0 && d[4 * i] + oh * ow * 3 <= stage.numel(), "hcb.jpeg_crop_rgb: crop ", i,
+                " outside the staging buffer");
+    for (int64_t c = 0; c < ncomp; ++c) {
+      const int64_t* f = r + 8 + 5 * c;
+      const int64_t fh = c == 0 ? 1 : hs, fv = c == 0 ? 1 : vs;
+      // samples of this plane the kernel reads: the crop, or its chroma taps clipped to the true plane
+      int64_t xlo = x0, xhi = x0 + ow * red - 1, ylo = y0, yhi = y0 + oh * red - 1;
+      if (fh == 2) {
+        xlo = std::max<int64_t>((x0 >> 1) - 1, 0);
+        xhi = std::min<int64_t>((xhi >> 1) + 1, (W + 1) / 2 - 1);
+      }
+      if (fv == 2) {
+        ylo = std::max<int64_t>((y0 >> 1) - 1, 0);
+        yhi = std::min<int64_t>((yhi >> 1) + 1, (H + 1) / 2 - 1);
+      }
+      TORCH_CHECK(f[1] >= 0 && f[2] >= 0 && f[3] > 0 && f[4] > 0 && f[3] <= 8192 && f[4] <= 8192 && f[1] <= 8192 &&
+                      f[2] <= 8192 && f[1] * 8 <= xlo && xhi < (f[1] + f[3]) * 8 && f[2] * 8 <= ylo &&
+                      yhi < (f[2] + f[4]) * 8,
+                  "hcb.jpeg_crop_rgb: block window of image ", i, " component ", c, " does not cover its crop");
+      TORCH_CHECK(f[0] >= 0 && f[0] + f[3] * f[4] * 64 <= planes.numel(), "hcb.jpeg_crop_rgb: plane of image ", i,
+                  " component ", c, " outside planes");
+    }
+    TORCH_CHECK(oh * ow < (1ll << 31), "hcb.jpeg_crop_rgb: crop ", i, " too large");
+    max_pixels = std::max(max_pixels, oh * ow);
+  }
+  if (max_pixels == 0) return;
+  hcb::launch_jpeg_crop_rgb(imgs.data_ptr<int64_t>(), desc.data_ptr<int64_t>(), (int)B, max_pixels,
+                            planes.data_ptr<uint8_t>(), stage.data_ptr<uint8_t>(), cur_stream());
+}
+
 // Plan-A shortcut (kernels/shortcut.hip): the geometry of x [N][H][W][C] (or its planes [3][N][H][W][C]) against
 // y [N][P][Q][K] at stride s, in 16-byte vectors; refuses what the kernels do not do, by name
 struct ShortcutGeom {
@@ -1616,6 +1732,8 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("preprocess_distort(Tensor src, Tensor desc, Tensor desc_host, Tensor params, Tensor params_host, "
         "Tensor(a!) out, Tensor(b!) work, float[] scale, float[] bias) -> ()");
   m.def("cifar_batch(Tensor data, Tensor labels_all, Tensor desc, Tensor desc_host, Tensor(a!) out, Tensor(b!) labels_out) -> ()");
+  m.def("jpeg_idct(Tensor coef, Tensor segs, Tensor segs_host, Tensor(a!) planes) -> ()");
+  m.def("jpeg_crop_rgb(Tensor planes, Tensor imgs, Tensor imgs_host, Tensor desc, Tensor desc_host, Tensor(a!) stage) -> ()");
   m.def("shortcut_pad_fwd(Tensor x, Tensor(a!) y, int s) -> ()");
   m.def("shortcut_pad_bwd(Tensor g, Tensor(a!) dx, int s) -> ()");
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
@@ -1683,6 +1801,8 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("preprocess_images", preprocess_images);
   m.impl("preprocess_distort", preprocess_distort);
   m.impl("cifar_batch", cifar_batch);
+  m.impl("jpeg_idct", jpeg_idct);
+  m.impl("jpeg_crop_rgb", jpeg_crop_rgb);
   m.impl("shortcut_pad_fwd", shortcut_pad_fwd);
   m.impl("shortcut_pad_bwd", shortcut_pad_bwd);
   m.impl("synth_labels", synth_labels);

@@ -16,8 +16,10 @@
 //   * a Prefetcher: reader threads over this rank's shards (file i -> rank i % world), a
 //     shuffle pool, epoch looping, and next_batch() that hands back (jpeg bytes, label, crop
 //     window, flip) with the GIL released while it waits.
-// JPEG entropy decoding stays in the Python layer (Pillow releases the GIL); resize / flip /
-// normalise / NHWC-bf16 packing is the HIP kernel `preprocess_images` (csrc/kernels/data.hip).
+// JPEG decoding is Pillow's in the Python layer (it releases the GIL) or, with --gpu_jpeg_decode,
+// jpeg.cpp's entropy decoder (bound below as jpeg_entropy_decode) followed by the jpeg_idct /
+// jpeg_crop_rgb kernels; resize / flip / normalise / NHWC-bf16 packing is the HIP kernel
+// `preprocess_images` (csrc/kernels/data.hip).
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -37,6 +39,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include "jpeg.h"
 
 namespace py = pybind11;
 
@@ -693,6 +697,30 @@ PYBIND11_MODULE(_hcb_data, m) {
       py::arg("H"), py::arg("W"), py::arg("boxes") = std::vector<std::tuple<float, float, float, float>>{},
       py::arg("seed") = 0, py::arg("min_object_covered") = 0.1f, py::arg("ar_lo") = 0.75f, py::arg("ar_hi") = 1.33f,
       py::arg("area_lo") = 0.05f, py::arg("area_hi") = 1.0f, py::arg("attempts") = 100);
+  // Entropy-decodes `jpeg` for the crop window (y, x, h, w) into the writable byte buffer `dst`
+  // (16-byte aligned; the record layout is csrc/data/jpeg.h). Returns the bytes written, or the string
+  // "declined: <reason>"; never raises on the JPEG's content. Runs with the GIL released.
+  m.def(
+      "jpeg_entropy_decode",
+      [](py::bytes jpeg, std::tuple<int, int, int, int> win, py::buffer dst) -> py::object {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(jpeg.ptr(), &p, &n) != 0) throw py::error_already_set();
+        py::buffer_info bi = dst.request(true);
+        if (bi.itemsize != 1 || bi.ndim != 1 || (bi.size > 1 && bi.strides[0] != 1))
+          throw std::invalid_argument("jpeg_entropy_decode: dst must be a contiguous 1-D byte buffer");
+        const char* why = "";
+        long r;
+        {
+          py::gil_scoped_release nogil;
+          r = hcbjpeg::jpeg_entropy_decode(reinterpret_cast<const uint8_t*>(p), (size_t)n, std::get<0>(win),
+                                           std::get<1>(win), std::get<2>(win), std::get<3>(win),
+                                           static_cast<uint8_t*>(bi.ptr), (size_t)bi.size, &why);
+        }
+        if (r < 0) return py::str(std::string("declined: ") + why);
+        return py::int_(r);
+      },
+      py::arg("jpeg"), py::arg("win"), py::arg("dst"));
   m.def("central_crop", [](int H, int W, float frac) {
     Window w = central_crop(H, W, frac);
     return py::make_tuple(w.y, w.x, w.h, w.w);

@@ -306,6 +306,18 @@ void launch_preprocess_distort(const uint8_t* src, const int64_t* desc, const fl
 void launch_cifar_batch(const uint8_t* data, const int64_t* labels_all, const int* desc, int B, void* out,
                         int64_t* labels_out, int Cpad, bool f32, hipStream_t st);
 
+// GPU JPEG decode (jpeg.hip), after the host's entropy decoder (csrc/data/jpeg.cpp). jpeg_idct: segment
+// table int64 [nseg][8] = (group0, nblocks, coefficient byte offset, record byte offset, quantisation
+// table, plane byte offset, 0, 0), group0 the exclusive prefix of ceil(nblocks / jpeg_idct_group_blocks());
+// coef: the records; planes: block-major uint8 scratch, written before it is read. jpeg_crop_rgb: image
+// table int64 [B][24] = (ncomp | 0 = skip, r, hs, vs, H, W, y0, x0, 3 x (plane byte offset, bx0, by0, bw,
+// bh), 0) and the (offset, h, w, flip) rows of preprocess_images -> packed RGB uint8 crops in stage
+int jpeg_idct_group_blocks();
+void launch_jpeg_idct(const int64_t* segs_dev, int nseg, int64_t groups, const uint8_t* coef, uint8_t* planes,
+                      hipStream_t st);
+void launch_jpeg_crop_rgb(const int64_t* imgs_dev, const int64_t* desc_dev, int B, int64_t max_pixels,
+                          const uint8_t* planes, uint8_t* stage, hipStream_t st);
+
 // ---------------------------------------------------------------- plan-A shortcut (shortcut.hip)
 // stride-s subsample + centred zero pad of the channels and its gradient, in 16-byte vectors: x / dx
 // [NI][H][W][Cv], y / g [NI][P][Q][Kv], Kv == Cv + 2 * padv, P == ceil(H / s), Q == ceil(W / s)
