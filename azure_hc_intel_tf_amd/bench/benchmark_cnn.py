@@ -28,21 +28,25 @@ from .flags import Params, compute_dtype_of, noop_flags_set, parse_flags
 MODEL_DEFAULT_BATCH = {"inception3": 32, "trivial": 32, "alexnet": 512, "googlenet": 32, "overfeat": 32,
                        "lenet": 32, "vgg11": 32, "vgg16": 32, "vgg19": 32,
                        "resnet20": 128, "resnet32": 128, "resnet44": 128, "resnet56": 128, "resnet110": 128}
+# a model name that is another network on another dataset: (dataset, name) -> its default batch
+DATASET_MODEL_DEFAULT_BATCH = {("cifar10", "alexnet"): 128}
 # --data_name: images per training epoch (--num_epochs, the Num epochs line)
 DATASET_EPOCH_IMAGES = {"imagenet": 1281167, "cifar10": 50000}
 
 
 def check_dataset(p: Params) -> str:
     """The dataset of a run (--data_name, default imagenet) and the model / flag combinations it refuses:
-    CIFAR-10 trains its own ResNets (and ``trivial``) at 32 x 32 and has neither colour distortion nor a
-    resize; those ResNets exist for CIFAR-10 only."""
-    from ..models import CIFAR_MODELS
+    CIFAR-10 trains its own ResNets, its own AlexNet (and ``trivial``) at 32 x 32 and has neither colour
+    distortion nor a resize; those ResNets exist for CIFAR-10 only, while ``alexnet`` without the flag is the
+    ImageNet model."""
+    from ..models import CIFAR_MODELS, dataset_model_names
 
     name = p.data_name or "imagenet"
     if name not in DATASET_EPOCH_IMAGES:
         raise ValueError(f"--data_name={name}: the datasets are {', '.join(DATASET_EPOCH_IMAGES)}")
     if name == "cifar10":
-        allowed = CIFAR_MODELS + ("trivial",)
+        # (alexnet: with this dataset the name is the CIFAR-10 AlexNet, models.create_model(data_name=))
+        allowed = CIFAR_MODELS + ("trivial",) + tuple(dataset_model_names("cifar10"))
         if p.model not in allowed:
             raise ValueError(f"--data_name=cifar10 runs the models {', '.join(allowed)}, not --model={p.model}")
         if p.color_distortions:
@@ -123,7 +127,8 @@ class BenchmarkCNN:
         else:
             self.device = torch.device("cpu")
         self.model_name = p.model
-        self.batch_size = p.batch_size or MODEL_DEFAULT_BATCH.get(p.model, 64)
+        self.batch_size = p.batch_size or DATASET_MODEL_DEFAULT_BATCH.get((self.data_name, p.model)) or \
+            MODEL_DEFAULT_BATCH.get(p.model, 64)
         self.num_batches = p.num_batches
         if p.num_warmup_batches is None:
             self.num_warmup_batches = 10 if self.on_gpu else 2
@@ -146,7 +151,7 @@ class BenchmarkCNN:
             from ..data.cifar10 import IMAGE_SIZE, NUM_CLASSES
 
             kw["image_size"], kw["num_classes"] = IMAGE_SIZE, NUM_CLASSES
-        self.model = create_model(p.model, **kw)
+        self.model = create_model(p.model, data_name=self.data_name, **kw)
         if p.num_epochs:
             self.num_batches = int(math.ceil(p.num_epochs * self.epoch_images / (self.batch_size * self.size)))
         self.step_offset = 0

@@ -47,7 +47,8 @@ FLAGS: List[Flag] = [
     Flag("num_batches", None, int, "timed steps (default 100; with --eval on real data and neither this nor "
          "--num_epochs given: one pass over the validation split)"),
     Flag("model", "trivial", str, "model name: resnet50|101|152[_v1.5], inception3, mobilenet, vgg11|16|19, alexnet, googlenet, "
-         "overfeat, lenet, trivial; with --data_name=cifar10: resnet20|32|44|56|110, trivial"),
+         "overfeat, lenet, trivial; with --data_name=cifar10: resnet20|32|44|56|110, trivial, alexnet (there the "
+         "CIFAR-10 AlexNet: two 5x5 convs with local response normalisation, default batch 128)"),
     Flag("num_intra_threads", 0, int, "host intra-op threads (CPU path: torch.set_num_threads)"),
     Flag("num_inter_threads", 0, int, "host inter-op threads (CPU path)"),
     Flag("kmp_blocktime", 0, int, "KMP_BLOCKTIME for the CPU path", noop_on_gpu=True),
@@ -80,7 +81,7 @@ FLAGS: List[Flag] = [
          "synthetic images of the dataset's size"),
     Flag("data_name", None, str, "dataset: imagenet (default; 224 x 224, 1001 classes, 1,281,167 images per epoch) | "
          "cifar10 (32 x 32, 11 classes, 50,000 images per epoch, held in device memory; models resnet20|32|44|56|110, "
-         "trivial)"),
+         "trivial, alexnet)"),
     Flag("datasets_num_private_threads", None, int, "TFRecord reader threads per worker (real data)"),
     Flag("num_decode_threads", None, int, "JPEG decode threads per worker (real data)"),
     Flag("distortions", True, parse_bool, "real-data training preprocessing: true = random distorted crop + flip "

@@ -83,14 +83,30 @@ _MODELS = {
 }
 
 
+# names that mean another network on another dataset (upstream's model_config keeps one table per
+# dataset): --model=alexnet --data_name=cifar10 is AlexnetCifar10Model, not the ImageNet AlexNet
+_DATASET_MODELS = {
+    "cifar10": {"alexnet": _seq("AlexNetCifar")},
+}
+
+
 def model_names():
     return sorted(_MODELS)
 
 
-def create_model(name: str, **kw) -> CNNModel:
+def dataset_model_names(data_name: str):
+    """The model names ``data_name`` gives a network of its own."""
+    return sorted(_DATASET_MODELS.get(data_name, {}))
+
+
+def create_model(name: str, data_name: str = None, **kw) -> CNNModel:
+    """``data_name``: the dataset of the run; a name the dataset overrides builds that dataset's network."""
+    override = _DATASET_MODELS.get(data_name or "imagenet", {})
+    if name in override:
+        return override[name](**kw)
     if name not in _MODELS:
         raise ValueError(f"unknown model {name!r}; available: {', '.join(model_names())}")
     return _MODELS[name](**kw)
 
 
-__all__ = ["create_model", "model_names", "CNNModel", "ResNet"]
+__all__ = ["create_model", "model_names", "dataset_model_names", "CNNModel", "ResNet"]

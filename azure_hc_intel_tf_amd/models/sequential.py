@@ -16,7 +16,7 @@ from __future__ import annotations
 
 from typing import List, Tuple
 
-from ..nn.layers import ConvBN, Dropout, GlobalAvgPool, Layer, Logits, Pool
+from ..nn.layers import LRN, ConvBN, Dropout, GlobalAvgPool, Layer, Logits, Pool
 from .base import CNNModel
 from .inception import InceptionModule
 
@@ -45,8 +45,11 @@ def inception_v1_cols(k, l, m, n, p, q):
 
 class SequentialCNN(CNNModel):
     """A model given as a list of layer specs:
-    ('conv', C, kh, kw[, sh, sw, mode]) | ('mpool'|'apool', kh, kw, sh, sw[, mode]) |
-    ('inception', cols) | ('gap',) | ('flatten',) | ('affine', N) | ('dropout',)."""
+    ('conv', C, kh, kw[, sh, sw, mode[, stddev, bias0]]) | ('mpool'|'apool', kh, kw, sh, sw[, mode]) |
+    ('inception', cols) | ('gap',) | ('flatten',) | ('affine', N[, stddev, bias0]) | ('dropout',) |
+    ('lrn', depth_radius, bias, alpha, beta).
+    ``stddev, bias0``: the kernel starts as a truncated normal of that stddev and the bias at the constant
+    bias0, in place of the Glorot-uniform kernel and zero bias."""
 
     specs: List[Tuple] = []
     # --compute_dtype fp32 on the HIP kernels: bf16x6 plane GEMMs with the bias + ReLU epilogue (fp32
@@ -56,6 +59,14 @@ class SequentialCNN(CNNModel):
     dropout_keep = 0.5
     default_batch_size = 32
     default_lr = 0.005
+
+    @staticmethod
+    def _init_kw(opt) -> dict:
+        """ConvBN's initialiser arguments from a spec's optional (stddev, bias0) tail."""
+        if not opt:
+            return dict(init="glorot")
+        stddev, bias0 = opt
+        return dict(init=("trunc_normal", stddev), bias_init=bias0)
 
     def build(self):
         ps = self.ps
@@ -69,7 +80,7 @@ class SequentialCNN(CNNModel):
                 c, kh, kw = op[1:4]
                 sh, sw, mode = (op[4], op[5], op[6]) if len(op) > 4 else (1, 1, "SAME")
                 layer = ConvBN(ps, name, shape, c, kh, kw, sh, sw, mode, relu=True, bn=False, need_dx=not first,
-                               logical_cin=3 if first else None, init="glorot")
+                               logical_cin=3 if first else None, **self._init_kw(op[7:]))
                 first = False
             elif kind in ("mpool", "apool"):
                 kh, kw, sh, sw = op[1:5]
@@ -83,9 +94,11 @@ class SequentialCNN(CNNModel):
                 layer = Flatten(name, shape)
             elif kind == "affine":
                 assert shape[0] == 1 and shape[1] == 1, f"{name}: affine needs a flattened input"
-                layer = ConvBN(ps, name, shape, op[1], 1, 1, relu=True, bn=False, init="glorot")
+                layer = ConvBN(ps, name, shape, op[1], 1, 1, relu=True, bn=False, **self._init_kw(op[2:]))
             elif kind == "dropout":
                 layer = Dropout(name, shape, self.dropout_keep, seed=len(self.seq))
+            elif kind == "lrn":
+                layer = LRN(name, shape, *op[1:5])
             else:
                 raise ValueError(kind)
             self.seq.append(layer)
@@ -155,6 +168,32 @@ class AlexNet(SequentialCNN):
     specs = [("conv", 64, 11, 11, 4, 4, "VALID"), ("mpool", 3, 3, 2, 2), ("conv", 192, 5, 5), ("mpool", 3, 3, 2, 2),
              ("conv", 384, 3, 3), ("conv", 384, 3, 3), ("conv", 256, 3, 3), ("mpool", 3, 3, 2, 2), ("flatten",),
              ("affine", 4096), ("dropout",), ("affine", 4096), ("dropout",)]
+
+
+class AlexNetCifar(SequentialCNN):
+    """tf_cnn_benchmarks ``--model=alexnet --data_name=cifar10`` (upstream ``AlexnetCifar10Model``), input 32 x 32:
+    conv 5x5 (64) -> mpool 3x3/2 -> lrn -> conv 5x5 (64) -> lrn -> mpool 3x3/2 -> affine 384 -> affine 192 ->
+    logits, everything 'SAME'; lrn(depth_radius 4, bias 1.0, alpha 0.001 / 9, beta 0.75); kernels truncated normal
+    (stddev 0.05 convs, 0.04 affines), biases 0.0 / 0.1 / 0.1 / 0.1; no dropout. 1,756,426 parameters at 10
+    classes, 1,756,619 at this project's 11. Learning rate 0.1, decayed by 0.1 every 100 epochs (staircase). The
+    values follow upstream from memory; they are not pinned against the upstream source."""
+
+    name = "alexnet"
+    default_image_size = 32
+    default_batch_size = 128
+    LRN_SPEC = ("lrn", 4, 1.0, 0.001 / 9.0, 0.75)
+    specs = [("conv", 64, 5, 5, 1, 1, "SAME", 0.05, 0.0), ("mpool", 3, 3, 2, 2, "SAME"), LRN_SPEC,
+             ("conv", 64, 5, 5, 1, 1, "SAME", 0.05, 0.1), LRN_SPEC, ("mpool", 3, 3, 2, 2, "SAME"), ("flatten",),
+             ("affine", 384, 0.04, 0.1), ("affine", 192, 0.04, 0.1)]
+
+    def __init__(self, num_classes: int = 11, **kw):
+        super().__init__(num_classes=num_classes, **kw)
+
+    @staticmethod
+    def lr_schedule(global_batch: int):
+        """tf.train.exponential_decay(0.1, step, 100 epochs of 50,000 images, 0.1, staircase=True)."""
+        decay_steps = 100 * int(50000 / global_batch)
+        return lambda step: 0.1 * 0.1 ** (step // decay_steps)
 
 
 class OverFeat(SequentialCNN):

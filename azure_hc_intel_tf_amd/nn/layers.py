@@ -214,8 +214,10 @@ class ConvBN(_BatchNorm):
     def __init__(self, ps: ParamStore, name: str, in_shape, cout: int, kh: int, kw: int, sh: int = 1,
                  sw: int = 1, mode="SAME", relu: bool = True, bn: bool = True, need_dx: bool = True,
                  eps: float = 1e-5, decay: float = 0.9, logical_cin: Optional[int] = None,
-                 dilation: int = 1, scale: bool = True, init: str = "variance_scaling", bias: bool = True,
-                 relu6: bool = False):
+                 dilation: int = 1, scale: bool = True, init="variance_scaling", bias: bool = True,
+                 relu6: bool = False, bias_init: float = 0.0):
+        """``init``: "variance_scaling" | "glorot" | ("trunc_normal", stddev) -- the kernel initialiser;
+        ``bias_init``: the constant the bias of a BN-free layer starts at."""
         H, W, cin = in_shape
         assert not relu6 or (relu and bn), "ReLU6 is the BN pass's activation"
         self.relu6 = relu6
@@ -234,15 +236,19 @@ class ConvBN(_BatchNorm):
         self.decay = decay
         lc = logical_cin or cin
         fan_in = kh * kw * lc
-        winit = (ps.glorot_uniform(fan_in, kh * kw * cout, lc if lc != cin else -1) if init == "glorot"
-                 else ps.variance_scaling(fan_in, lc if lc != cin else -1))
+        if isinstance(init, tuple):
+            assert init[0] == "trunc_normal", init
+            winit = ps.trunc_normal_padded(init[1], lc if lc != cin else -1)
+        else:
+            winit = (ps.glorot_uniform(fan_in, kh * kw * cout, lc if lc != cin else -1) if init == "glorot"
+                     else ps.variance_scaling(fan_in, lc if lc != cin else -1))
         self.w = ps.add(f"{name}/conv2d/kernel", (cout, kh, kw, cin), True, winit, logical_numel=cout * kh * kw * lc)
         self.pack = ps.add_pack(self.w, cout, kh, kw, cin, self.spec.Kpad, self.spec.Kpad_t, want_tr=need_dx)
         if bn:
             self._init_bn(ps, name, cout, scale)
         else:
             # ResNet-v2's un-normalised convs (shortcut, conv3) have no bias in tf_cnn_benchmarks
-            self.bias = ps.add(f"{name}/conv2d/bias", (cout,), True, ParamStore.const(0.0)) if bias else None
+            self.bias = ps.add(f"{name}/conv2d/bias", (cout,), True, ParamStore.const(bias_init)) if bias else None
         self._saved = None
         self._pre_reduced = False
         self.training = True  # False: inference BN from the moving statistics (forward-only)
@@ -748,6 +754,42 @@ class Pool(Layer):
             accumulate = False
         Fn.pool_backward(dy, x, y, dx, *self.k, *self.s, self.pads, self.is_max, self.incl_pad, accumulate,
                          argmax=amax)
+        self._saved = None
+        return dx
+
+    def clear(self):
+        self._saved = None
+
+
+class LRN(Layer):
+    """Local response normalisation over the channels (tf_cnn_benchmarks ``cnn.lrn``, tf.nn.lrn): y = x *
+    (bias + alpha * sum_{|j - d| <= depth_radius} x[j]^2)^(-beta), alpha not divided by the window size.
+    No parameters; training and inference are one computation. On the GPU it is the pair of kernels of
+    csrc/kernels/lrn.hip: 16-bit in / out, or on the fp32 path fp32 or Planes in and always Planes out (its
+    consumers, a conv or a pool, take planes). The backward recomputes the scale from the saved input and
+    writes a plain dx."""
+
+    def __init__(self, name, in_shape, depth_radius: int, bias: float, alpha: float, beta: float):
+        self.name = name
+        self.in_shape = in_shape
+        self.out_shape = in_shape
+        self.r, self.bias, self.alpha, self.beta = int(depth_radius), float(bias), float(alpha), float(beta)
+        self._saved = None
+
+    def forward(self, x):
+        if Fn.native(x) and not Fn.is_planes(x) and not x.is_contiguous():
+            x = x.contiguous()  # (a concat-window view)
+        shape = tuple(x.shape)
+        y = empty_op(shape, x.device) if Fn.native(x) else torch.empty(shape, dtype=x.dtype, device=x.device)
+        Fn.lrn_forward(x, y, self.r, self.bias, self.alpha, self.beta)
+        self._saved = x
+        return y
+
+    def backward(self, dy):
+        x = self._saved
+        dx = empty_act(tuple(x.shape), dy.device)
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        Fn.lrn_backward(dy, x, dx, self.r, self.bias, self.alpha, self.beta)
         self._saved = None
         return dx
 

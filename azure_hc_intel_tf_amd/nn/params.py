@@ -145,6 +145,18 @@ class ParamStore:
 
         return f
 
+    def trunc_normal_padded(self, std: float, logical_c: int = -1):
+        """trunc_normal(std) for a conv kernel [cout, kh, kw, cin]; channels beyond ``logical_c`` (the input
+        padding of a first layer) are zero."""
+        tn = self.trunc_normal(std)
+
+        def f(t):
+            tn(t)
+            if logical_c > 0 and t.dim() == 4 and t.shape[3] > logical_c:
+                t[..., logical_c:] = 0
+
+        return f
+
     def variance_scaling(self, fan_in: int, logical_c: int = -1):
         """tf.variance_scaling_initializer() (scale 1, fan_in, truncated normal); channels
         beyond ``logical_c`` (input padding of the stem) are zero."""

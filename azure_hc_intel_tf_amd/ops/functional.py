@@ -1455,6 +1455,81 @@ def shortcut_pad_backward(g, dx, s: int):
     return dx
 
 
+# ---------------------------------------------------- local response normalisation
+LRN_NATIVE_MAX_R = 4    # the kernels' halo is one lane (8 channels) on each side
+LRN_NATIVE_MAX_C = 512  # the C / 8 lanes of a pixel share one 64-lane wave
+
+
+def _lrn_check(x, r: int, bias: float, alpha: float, others=()):
+    """The host-side refusals of lrn_forward / lrn_backward, each naming its argument."""
+    if not bias > 0:
+        raise ValueError(f"lrn: bias must be > 0, got bias={bias}")
+    if alpha < 0:
+        raise ValueError(f"lrn: alpha must be >= 0, got alpha={alpha}")
+    if int(r) != r or r < 1:
+        raise ValueError(f"lrn: depth_radius r must be an integer >= 1, got r={r}")
+    if x.dim() != 4:
+        raise ValueError(f"lrn: x must be [N, H, W, C], got {tuple(x.shape)}")
+    if native(x):
+        C = x.shape[-1]
+        if r > LRN_NATIVE_MAX_R:
+            raise ValueError(f"lrn: the HIP kernels take r <= {LRN_NATIVE_MAX_R} (a halo of one 8-channel lane), got r={r}")
+        if C % 8 != 0:
+            raise ValueError(f"lrn: the HIP kernels take C % 8 == 0 (16-byte channel vectors), got C={C}")
+        if C > LRN_NATIVE_MAX_C:
+            raise ValueError(f"lrn: the HIP kernels take C <= {LRN_NATIVE_MAX_C} (a pixel's lanes share one wave), got C={C}")
+        for name, t in (("x", x),) + tuple(others):
+            if not t.is_contiguous():
+                raise ValueError(f"lrn: {name} must be contiguous (the HIP kernels take no strided views)")
+
+
+def _lrn_window_sum(t, r: int):
+    """out[..., d] = sum_{j = max(0, d-r) .. min(C-1, d+r)} t[..., j] (PyTorch, t's dtype)."""
+    C = t.shape[-1]
+    tp = F.pad(t, (r, r))
+    acc = tp[..., 0:C].clone()
+    for j in range(1, 2 * r + 1):
+        acc += tp[..., j:j + C]
+    return acc
+
+
+def _lrn_scale(x, r: int, bias: float, alpha: float):
+    return bias + alpha * _lrn_window_sum(x * x, r)
+
+
+def lrn_forward(x, out, r: int, bias: float, alpha: float, beta: float):
+    """Local response normalisation over the channels of NHWC ``x`` with TensorFlow's semantics (tf.nn.lrn,
+    tf_cnn_benchmarks' ``cnn.lrn``): s[d] = bias + alpha * sum of x[j]^2 over |j - d| <= r inside [0, C), y =
+    x * s^(-beta); ``alpha`` is NOT divided by the window size (torch's local_response_norm with alpha * (2r+1)).
+    GPU (csrc/kernels/lrn.hip): x 16-bit -> out 16-bit; x fp32 or Planes -> out fp32 or Planes; r <= 4,
+    C % 8 == 0, C <= 512, contiguous tensors. CPU / non-native tensors: the formula in PyTorch at x's dtype
+    (any r)."""
+    _lrn_check(x, r, bias, alpha, (("out", out),))
+    if native(x):
+        assert tuple(out.shape) == tuple(x.shape), "lrn_forward: out has x's shape"
+        _ext.ops().lrn_fwd(_pl(x), _pl(out), int(r), float(bias), float(alpha), float(beta))
+        return out
+    out.copy_(x * _lrn_scale(x, int(r), bias, alpha) ** (-beta))
+    return out
+
+
+def lrn_backward(dy, x, dx, r: int, bias: float, alpha: float, beta: float):
+    """The gradient of lrn_forward, with s recomputed from the saved input ``x`` (no scale tensor is kept):
+    dx[j] = dy[j] * s[j]^(-beta) - 2 alpha beta x[j] * sum_{d: |d - j| <= r} dy[d] x[d] s[d]^(-beta-1).
+    GPU: ``dy`` / ``dx`` are plain activations (16-bit with a 16-bit x, fp32 with an fp32 or Planes x); every
+    element of ``dx`` is written."""
+    _lrn_check(x, r, bias, alpha, (("dy", dy), ("dx", dx)))
+    if native(x):
+        assert tuple(dy.shape) == tuple(x.shape) and tuple(dx.shape) == tuple(x.shape), "lrn_backward: shapes"
+        _ext.ops().lrn_bwd(dy, _pl(x), dx, int(r), float(bias), float(alpha), float(beta))
+        return dx
+    r = int(r)
+    s = _lrn_scale(x, r, bias, alpha)
+    t = dy * x * s ** (-beta - 1)
+    dx.copy_(dy * s ** (-beta) - (2 * alpha * beta) * x * _lrn_window_sum(t, r))
+    return dx
+
+
 # ------------------------------------------------------------------------- loss
 def softmax_xent(logits, labels, ncls, row_loss, dlogits, scale, scale_dev=None, dl32=None,
                  label_smoothing: float = 0.0):

@@ -1423,6 +1423,85 @@ void shortcut_pad_bwd(const Tensor& g, const Tensor& dx, int64_t s) {
   hcb::launch_shortcut_pad_bwd(g.data_ptr(), dx.data_ptr(), q.NI, q.H, q.W, q.P, q.Q, q.s, q.Cv, q.Kv, q.padv, cur_stream());
 }
 
+// Local response normalisation (kernels/lrn.hip). A tensor is [N][H][W][C] of the build's 16-bit type
+// (format 0) or fp32 (1), or bf16 planes [3][N][H][W][C] (2); returns the format and the logical shape
+int lrn_format(const Tensor& t, const char* name, const char* op, std::vector<int64_t>* shape, int64_t* plane) {
+  check_cuda(t, name);
+  const auto dt = t.scalar_type();
+  int f;
+  if (t.dim() == 5) {
+    TORCH_CHECK(dt == at::kBFloat16 && t.size(0) == 3, "hcb.", op, ": ", name,
+                " has 5 dims but is not bf16 planes [3][N][H][W][C]");
+    f = 2;
+  } else {
+    TORCH_CHECK(t.dim() == 4, "hcb.", op, ": ", name, " must be [N][H][W][C] (or bf16 planes [3][N][H][W][C])");
+    TORCH_CHECK(dt == kAct || dt == at::kFloat, "hcb.", op, ": ", name, " must be " HCB_ACT_NAME " or float32");
+    f = dt == kAct ? 0 : 1;
+  }
+  TORCH_CHECK(t.is_contiguous(), "hcb.", op, ": ", name, " must be contiguous (no strided views)");
+  check_align16(t.data_ptr(), name);
+  check_range(t, t.numel() * (int64_t)t.element_size(), name);
+  *shape = t.sizes().vec();
+  if (f == 2) shape->erase(shape->begin());
+  *plane = f == 2 ? t.stride(0) : 0;
+  return f;
+}
+
+hcb::LrnParams lrn_params(const std::vector<int64_t>& shape, int64_t r, double bias, double alpha, double beta,
+                          const char* op) {
+  const int64_t C = shape[3], M = shape[0] * shape[1] * shape[2];
+  TORCH_CHECK(M >= 1, "hcb.", op, ": empty tensor");
+  TORCH_CHECK(C >= 8 && C % 8 == 0, "hcb.", op, ": C must be a multiple of 8, got C = ", C);
+  TORCH_CHECK(C <= 512, "hcb.", op, ": C must be <= 512 (the C / 8 lanes of a pixel share one wave), got C = ", C);
+  TORCH_CHECK(r >= 1 && r <= 4, "hcb.", op, ": depth_radius r must be in 1..4 (a halo of one lane), got r = ", r);
+  TORCH_CHECK(bias > 0 && std::isfinite(bias), "hcb.", op, ": bias must be > 0, got ", bias);
+  TORCH_CHECK(alpha >= 0 && std::isfinite(alpha), "hcb.", op, ": alpha must be >= 0, got ", alpha);
+  TORCH_CHECK(std::isfinite(beta), "hcb.", op, ": beta must be finite");
+  TORCH_CHECK(M * C < (1ll << 40) && hcb::lrn_blocks(M, (int)C) < (1ll << 31), "hcb.", op, ": tensor too large");
+  hcb::LrnParams p{};
+  p.M = M;
+  p.C = (int)C;
+  p.r = (int)r;
+  p.bias = (float)bias;
+  p.alpha = (float)alpha;
+  p.beta = (float)beta;
+  p.pmode = beta == 0.75 ? 1 : (beta == 0.5 ? 2 : 0);
+  return p;
+}
+
+void lrn_fwd(const Tensor& x, const Tensor& y, int64_t r, double bias, double alpha, double beta) {
+  std::vector<int64_t> xs, ys;
+  int64_t xpl, ypl;
+  const int xf = lrn_format(x, "x", "lrn_fwd", &xs, &xpl), yf = lrn_format(y, "y", "lrn_fwd", &ys, &ypl);
+  TORCH_CHECK(x.device() == y.device(), "hcb.lrn_fwd: both tensors on one device");
+  TORCH_CHECK(xs == ys, "hcb.lrn_fwd: y must have x's shape");
+  TORCH_CHECK((xf == 0) == (yf == 0), "hcb.lrn_fwd: a 16-bit x writes a 16-bit y; an fp32 or planes x writes fp32 or planes");
+  hcb::LrnParams p = lrn_params(xs, r, bias, alpha, beta, "lrn_fwd");
+  p.x = x.data_ptr();
+  p.x_plane = xpl;
+  p.out = y.data_ptr();
+  p.out_plane = ypl;
+  hcb::launch_lrn_fwd(p, xf, yf, cur_stream());
+}
+
+// dy / dx: plain activations (16-bit with a 16-bit x, fp32 with an fp32 or planes x); every element of dx is written
+void lrn_bwd(const Tensor& dy, const Tensor& x, const Tensor& dx, int64_t r, double bias, double alpha, double beta) {
+  std::vector<int64_t> xs, gs, ds;
+  int64_t xpl, gpl, dpl;
+  const int xf = lrn_format(x, "x", "lrn_bwd", &xs, &xpl);
+  const int gf = lrn_format(dy, "dy", "lrn_bwd", &gs, &gpl), df = lrn_format(dx, "dx", "lrn_bwd", &ds, &dpl);
+  TORCH_CHECK(x.device() == dy.device() && x.device() == dx.device(), "hcb.lrn_bwd: all tensors on one device");
+  TORCH_CHECK(xs == gs && xs == ds, "hcb.lrn_bwd: dy and dx must have x's shape");
+  TORCH_CHECK(gf == df && gf == (xf == 0 ? 0 : 1),
+              "hcb.lrn_bwd: dy and dx are plain activations, 16-bit with a 16-bit x, float32 with an fp32 or planes x");
+  hcb::LrnParams p = lrn_params(xs, r, bias, alpha, beta, "lrn_bwd");
+  p.x = x.data_ptr();
+  p.x_plane = xpl;
+  p.dy = dy.data_ptr();
+  p.out = dx.data_ptr();
+  hcb::launch_lrn_bwd(p, xf, cur_stream());
+}
+
 static int pack_mode(const Tensor& t, const char* what) {
   switch (t.scalar_type()) {
     case at::kFloat: return 0;
@@ -1736,6 +1815,8 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("jpeg_crop_rgb(Tensor planes, Tensor imgs, Tensor imgs_host, Tensor desc, Tensor desc_host, Tensor(a!) stage) -> ()");
   m.def("shortcut_pad_fwd(Tensor x, Tensor(a!) y, int s) -> ()");
   m.def("shortcut_pad_bwd(Tensor g, Tensor(a!) dx, int s) -> ()");
+  m.def("lrn_fwd(Tensor x, Tensor(a!) y, int r, float bias, float alpha, float beta) -> ()");
+  m.def("lrn_bwd(Tensor dy, Tensor x, Tensor(a!) dx, int r, float bias, float alpha, float beta) -> ()");
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
         "Tensor(e!) run_mean, Tensor(f!) run_var, Tensor? shift=None) -> ()");
@@ -1805,6 +1886,8 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("jpeg_crop_rgb", jpeg_crop_rgb);
   m.impl("shortcut_pad_fwd", shortcut_pad_fwd);
   m.impl("shortcut_pad_bwd", shortcut_pad_bwd);
+  m.impl("lrn_fwd", lrn_fwd);
+  m.impl("lrn_bwd", lrn_bwd);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);

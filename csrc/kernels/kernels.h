@@ -326,6 +326,28 @@ void launch_shortcut_pad_fwd(const void* x, void* y, int64_t NI, int H, int W, i
 void launch_shortcut_pad_bwd(const void* g, void* dx, int64_t NI, int H, int W, int P, int Q, int s, int Cv, int Kv,
                              int padv, hipStream_t st);
 
+// ---------------------------------------------------------------- local response normalisation (lrn.hip)
+// tf.nn.lrn over the channels of M = N*H*W contiguous pixels of C channels (C % 8 == 0, C <= 512),
+// radius r in 1..4: s = bias + alpha * sum_{|j - d| <= r} x[j]^2, y = x * s^(-beta). Tensor formats: 0 = the
+// build's 16-bit type, 1 = fp32, 2 = bf16 hi / mid / lo planes (`*_plane` elements apart). pmode: 1 when
+// beta == 0.75, 2 when beta == 0.5 (rsqrt / sqrt forms), else 0 (exp2 / log2).
+struct LrnParams {
+  const void* x;    // the input (backward: the saved input; s is recomputed from it)
+  int64_t x_plane;
+  const void* dy;   // backward: the upstream gradient (format 0 or 1, that of `out`)
+  void* out;        // forward: y; backward: dx
+  int64_t out_plane;
+  int64_t M;
+  int C, r;
+  float bias, alpha, beta;
+  int pmode;
+};
+int64_t lrn_blocks(int64_t M, int C);
+// format pairs: x 0 -> y 0; x 1 | 2 -> y 1 | 2
+void launch_lrn_fwd(const LrnParams& p, int xf, int yf, hipStream_t st);
+// x 0 -> dy / dx 0; x 1 | 2 -> dy / dx 1
+void launch_lrn_bwd(const LrnParams& p, int xf, hipStream_t st);
+
 // ---------------------------------------------------------------- space-to-depth stem (stem.hip)
 void launch_stem_s2d_f32(const float* x, int N, int H, int W, int ldx, uint16_t* out, int64_t plane, int Hs, int Ws,
                          int pad, hipStream_t st);

@@ -29,7 +29,7 @@ sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from azure_hc_intel_tf_amd.models import create_model  # noqa: E402
 from azure_hc_intel_tf_amd.models import sequential  # noqa: E402
 from azure_hc_intel_tf_amd.models.sequential import Flatten  # noqa: E402
-from azure_hc_intel_tf_amd.nn.layers import ConvBN, Dropout, Pool, set_gpu_compute_dtype  # noqa: E402
+from azure_hc_intel_tf_amd.nn.layers import LRN, ConvBN, Dropout, Pool, set_gpu_compute_dtype  # noqa: E402
 from azure_hc_intel_tf_amd.ops import functional as Fn  # noqa: E402
 from azure_hc_intel_tf_amd.trainer import Trainer, constant_lr, synthetic_batch  # noqa: E402
 
@@ -97,6 +97,10 @@ def mirror_grads(model_cpu, images, labels, decisions):
                 x = win.mean(-1)
         elif isinstance(l, Flatten):
             x = x.reshape(x.shape[0], 1, 1, -1)
+        elif isinstance(l, LRN):  # no decision in it: torch's own op (alpha per window, not per tap)
+            n = 2 * l.r + 1
+            x = F.local_response_norm(x.permute(0, 3, 1, 2), n, alpha=l.alpha * n, beta=l.beta,
+                                      k=l.bias).permute(0, 2, 3, 1)
         elif isinstance(l, Dropout):
             assert l.keep >= 1.0
         else:
@@ -113,12 +117,14 @@ def _flat(model, g):
     return torch.cat([g[p.name].reshape(-1) for p in model.ps.params])
 
 
-def probe(name: str, size: int, batch: int, seed: int = 9, img_seed: int = 4, verbose: bool = True):
+def probe(name: str, size: int, batch: int, seed: int = 9, img_seed: int = 4, verbose: bool = True,
+          data_name: str = None):
     """Returns a dict: per-layer flip counts (GPU vs CPU and vs the fp64 mirror) and the relative
-    gradient errors GPU / CPU vs the decision-forced fp64 mirrors."""
+    gradient errors GPU / CPU vs the decision-forced fp64 mirrors. ``data_name``: the dataset whose
+    network ``name`` means (cifar10: the CIFAR-10 AlexNet)."""
     old_keep = sequential.SequentialCNN.dropout_keep
     sequential.SequentialCNN.dropout_keep = 1.0
-    kw = dict(image_size=size, seed=seed, image_channels=8)
+    kw = dict(image_size=size, seed=seed, image_channels=8, data_name=data_name)
     try:
         mg = create_model(name, device="cuda", compute_dtype="fp32", **kw)
         mc = create_model(name, device="cpu", **kw)
