@@ -35,6 +35,8 @@ def _table_path(v):
 DEFAULT_CACHE = _table_path(os.environ.get("HCB_TUNED_TABLE")) or os.path.join(_DIR, "mi355x.json")
 # bump whenever the kernel config set changes: entries of another version are re-tuned
 CACHE_VERSION = 6  # 5: keys carry the filter tap count; 6: round-5 pruned cfgs / stream-K plans gone
+# (no bump for retiring the stream-K kernels of plane cfg 23-28: a retired number keeps a defined
+# meaning, its fallback (gemm_cfg.h K_RETIRED), and a bump would throw the shipped table away)
 
 
 def _entry_valid(key, val) -> bool:

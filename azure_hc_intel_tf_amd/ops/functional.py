@@ -570,16 +570,14 @@ _P3_TILES = {0: (128, 64), 1: (64, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64)
              7: (128, 128), 8: (128, 128), 9: (128, 128), 10: (256, 128), 11: (128, 256), 12: (64, 128),
              13: (128, 64), 14: (128, 64), 15: (64, 128), 16: (64, 64), 17: (64, 64),
              18: (64, 128), 19: (128, 64), 20: (64, 64), 21: (64, 64), 22: (128, 128),
-             23: (64, 128), 24: (128, 64), 25: (64, 64), 26: (64, 64), 27: (128, 128), 28: (128, 128),
              31: (64, 256), 32: (128, 256), 33: (64, 64), 34: (128, 64),
              35: (128, 64), 36: (128, 128)}
 # workgroups per CU each plane-GEMM cfg is built for
-_P3_OCC = {14: 2, 15: 2, 16: 2, 17: 3, 18: 2, 19: 2, 20: 2, 21: 3, 23: 2, 24: 2, 25: 2, 26: 3}
+_P3_OCC = {14: 2, 15: 2, 16: 2, 17: 3, 18: 2, 19: 2, 20: 2, 21: 3}
 # persistent short-K twins (conv_p3_persist.h): one workgroup per resident slot walks its tiles with
 # the LDS-DMA ring running across tile boundaries and a register epilogue; no split-K (a problem
 # with an epilogue they do not serve -- fused BN backward, beta, bias -- runs the twin)
-_P3_PERSIST = {18: 15, 19: 14, 20: 16, 21: 17, 22: 7, 23: 15, 24: 14, 25: 16, 26: 17, 27: 7, 28: 8,
-               31: 15, 32: 15, 33: 16, 34: 14, 35: 14, 36: 7}
+_P3_PERSIST = {18: 15, 19: 14, 20: 16, 21: 17, 22: 7, 31: 15, 32: 15, 33: 16, 34: 14, 35: 14, 36: 7}
 # the persistent kernel with each workgroup's weight slice resident in LDS (conv_p3_persist.h BRES):
 # every k-step's planes of one N tile (K x BN x 6 B) beside the A ring; cfg -> ring slots
 _P3_BRES = {31: 3, 32: 2, 33: 3, 34: 2, 35: 2, 36: 2}
@@ -622,10 +620,16 @@ def p3_bres_fits(cfg: int, N: int, K: int) -> bool:
     bm, bn = _P3_TILES[cfg]
     kpad = -(-K // 64) * 64
     return _P3_BRES[cfg] * 3 * bm * 64 + kpad * 3 * bn * 2 + 4 * N <= 160 * 1024
-# their STREAM-K form (conv_p3_persist.h SK): every workgroup a contiguous, equal share of all (tile,
-# k-step) iterations -- no wave-quantization tail; split tiles meet through the split-K workspace.
-# sk cfg -> the cfg it falls back to (the whole-tile persistent form; 28 -- cfg 8's geometry -- cfg 8)
-_P3_STREAMK = {23: 18, 24: 19, 25: 20, 26: 21, 27: 22, 28: 8}  # (29 / 30 retired: profiles/r6_quantization_streamk.txt)
+
+
+# cfg 23-30 were the stream-K form of the persistent kernels: measured slower on every layer and removed
+# (profiles/r4v_streamk_probe.txt, profiles/r6_quantization_streamk.txt). The numbers stay valid in
+# gemm_cfg.h, where each runs the cfg it used to fall back to, so an old plan that names one still
+# launches; they are in none of the tables above and no candidate list offers them.
+# retired cfg -> the per-tile cfg its fallback chain ends at (the inference epilogue's kernels)
+_P3_RETIRED = {23: 15, 24: 14, 25: 16, 26: 17, 27: 7, 28: 8, 29: 10, 30: 11}
+
+
 # wgrad cfg -> block tile: 0-5 64-deep slots, 6-11 32-deep slots (128x128 / 256x128 / 128x256 tiles),
 # 12-15 32-deep slots, two / three workgroups per CU
 _WP3_TILES = {0: (128, 64), 1: (64, 128), 2: (64, 64), 3: (128, 64), 4: (64, 128), 5: (64, 64),
@@ -648,7 +652,7 @@ def p3_candidates(M: int, N: int, K: int):
     split-K factors that bring the grid close to whole rounds of the 256 CUs (one workgroup fits per
     CU: 144 KB of LDS) -- a 196-tile layer leaves 60 CUs idle, 4 splits run it in 3.06 rounds --
     while every split keeps >= 2 64-deep k-steps. (Stream-K shares were measured 11-30% slower per
-    layer and removed: profiles/r4v_streamk_probe.txt, profiles/r5_prune_variants.txt.)"""
+    layer and removed, cfg 23-30: profiles/r4v_streamk_probe.txt, profiles/r6_quantization_streamk.txt.)"""
     out = []
     ksteps = math.ceil(K / 64)
     for c, (bm, bn) in _P3_TILES.items():
@@ -718,9 +722,9 @@ def wgrad_p3_plan(Nout: int, K: int, M: int, taps: int = 1):
     return c, splits
 
 
-def _plan(cfg, M, N, K, device, taps: int = 1, planner=conv_plan, clamp_k: bool = False, ws_cfgs=()):
+def _plan(cfg, M, N, K, device, taps: int = 1, planner=conv_plan, clamp_k: bool = False):
     """Normalise a cfg argument (None = tuned / heuristic, int, or (cfg, splits)). ``clamp_k``: at most
-    K // 64 splits; ``ws_cfgs``: the cfgs that need the split-K workspace with one split (stream-K)."""
+    K // 64 splits."""
     if cfg is None:
         cfg, splits = planner(M, N, K, taps)
     elif isinstance(cfg, (tuple, list)):
@@ -731,13 +735,13 @@ def _plan(cfg, M, N, K, device, taps: int = 1, planner=conv_plan, clamp_k: bool 
         splits = max(1, min(int(splits), max(K // 64, 1)))
     if _DET[0]:
         splits = 1
-    if splits > 1 or int(cfg) in ws_cfgs:
+    if splits > 1:
         ensure_splitk_workspace(device)
     return int(cfg), int(splits)
 
 
 # what the plane (fp32) GEMMs' plan adds to the 16-bit one
-_P3_PLAN = dict(planner=p3_plan, clamp_k=True, ws_cfgs=_P3_STREAMK)
+_P3_PLAN = dict(planner=p3_plan, clamp_k=True)
 
 
 _SPLITS = ConvGeom._fields.index("splits")
@@ -1103,7 +1107,7 @@ def conv_bn_inference(x, spec: ConvSpec, wpack, w_master, gamma, beta, running_m
     or on the fp32 path Planes (``out`` Planes) or fp32; no raw conv output is stored. ``residual`` is
     read in ``out``'s format (converted once when it arrives in the other one). ``cfg``: None (the
     forward plan), an int or (cfg, splits); a cfg without the inference epilogue (the persistent /
-    stream-K / weights-resident plane GEMMs, the 3x3 patch kernels) runs its per-tile twin. CPU and
+    weights-resident plane GEMMs, a retired number, the 3x3 patch kernels) runs its per-tile twin. CPU and
     GPU non-native: exactly conv_forward followed by bn_inference."""
     N, H, W, _ = x.shape
     P, Q = spec.out_hw(H, W)
@@ -1120,7 +1124,8 @@ def conv_bn_inference(x, spec: ConvSpec, wpack, w_master, gamma, beta, running_m
             residual = to_planes(residual) if is_planes(out) else from_planes(residual)
     cfg, splits = _plan(cfg, M, spec.cout, spec.K, x.device, spec.kh * spec.kw, **(_P3_PLAN if p3 else {}))
     if p3:
-        cfg = _P3_PERSIST.get(_P3_PATCH_FB.get(cfg, cfg), _P3_PATCH_FB.get(cfg, cfg))
+        cfg = _P3_PATCH_FB.get(cfg, cfg)
+        cfg = _P3_PERSIST.get(cfg, _P3_RETIRED.get(cfg, cfg))
     elif cfg in PATCH_CFGS:  # no split-K on the twin, as launch_conv_igemm's own fallback
         cfg, splits = _PATCH_TWIN[cfg], 1
     if residual is not None:

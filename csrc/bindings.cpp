@@ -1649,13 +1649,6 @@ hcb::ConvParams p3_params(const Tensor& x, const Tensor& w, const Tensor& w_lo, 
   TORCH_CHECK(!stats_shift.has_value() || p.stats != nullptr, "hcb.conv_p3: stats_shift without stats");
   p.stats_shift = opt_f32(stats_shift, p.Nout, "stats_shift");
   attach_splitk(p, bm, bn, "conv_p3");
-  if (hcb::p3_cfg_streamk((int)cfg)) {  // stream-K (conv_p3_persist.h): the launcher sizes its shares against the workspace
-    TORCH_CHECK(g_splitk_ws != nullptr && g_splitk_cnt != nullptr, "hcb.conv_p3: stream-K needs the split-K workspace");
-    p.ws = g_splitk_ws;
-    p.cnt = g_splitk_cnt;
-  }
-  p.ws_floats = p.ws != nullptr ? g_splitk_ws_bytes / 4 : 0;
-  p.cnt_n = p.cnt != nullptr ? (int)g_splitk_cnt_n : 0;
   return p;
 }
 

@@ -27,14 +27,13 @@
 
 namespace hcb {
 
-// The rows of gemm_cfg.h HCB_P3_CFGS beyond the per-tile kernels: the persistent, stream-K and
+// The rows of gemm_cfg.h HCB_P3_CFGS beyond the per-tile kernels: the persistent and
 // weights-resident launchers return false for a problem they do not serve (an epilogue, a shape);
-// the row's fallback then runs, down to a per-tile cfg, which is returned. -1: launched.
+// the row's fallback then runs (a retired row's always), down to a per-tile cfg, which is returned.
+// -1: launched.
 #define HCB_CASE_TILE(...)
 #define HCB_CASE_PERSIST(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
   case C: return launch_p3p<WM, WN, TM, TN, KW, NST, OCC>(p, st) ? -1 : launch_p3_persist(p, FB, st);
-#define HCB_CASE_STREAMK(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
-  case C: return launch_p3sk<WM, WN, TM, TN, KW, NST, OCC>(p, st) ? -1 : launch_p3_persist(p, FB, st);
 #define HCB_CASE_BRES(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
   case C: return launch_p3bres<WM, WN, TM, TN, KW, NST>(p, st) ? -1 : launch_p3_persist(p, FB, st);
 #define HCB_CASE_RETIRED(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
@@ -47,7 +46,6 @@ static int launch_p3_persist(const ConvParams& p, int cfg, hipStream_t st) {
 }
 #undef HCB_CASE_TILE
 #undef HCB_CASE_PERSIST
-#undef HCB_CASE_STREAMK
 #undef HCB_CASE_BRES
 #undef HCB_CASE_RETIRED
 

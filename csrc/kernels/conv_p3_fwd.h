@@ -278,7 +278,6 @@ static void launch_p3(const ConvParams& p, hipStream_t st) {
 #define HCB_CASE_TILE(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
   case C: launch_p3<WM, WN, TM, TN, KW, NST, OCC, BNB, INF>(p, st); break;
 #define HCB_CASE_PERSIST(...)
-#define HCB_CASE_STREAMK(...)
 #define HCB_CASE_BRES(...)
 #define HCB_CASE_RETIRED(...)
 template <bool BNB, bool INF>
@@ -290,7 +289,6 @@ static void launch_p3_cfg(const ConvParams& p, int cfg, hipStream_t st) {
 }
 #undef HCB_CASE_TILE
 #undef HCB_CASE_PERSIST
-#undef HCB_CASE_STREAMK
 #undef HCB_CASE_BRES
 #undef HCB_CASE_RETIRED
 

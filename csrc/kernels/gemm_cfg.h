@@ -21,8 +21,7 @@ enum GemmKind {
   K_KQ = 3,       // weight grad with an intra-workgroup k-split over KS wave groups
   K_TILE = 4,     // plane GEMM, one workgroup per tile
   K_PERSIST = 5,  // plane GEMM, persistent workgroups (conv_p3_persist.h)
-  K_STREAMK = 6,  // ... its stream-K form
-  K_BRES = 7,     // ... with the workgroup's weight slice resident in LDS
+  K_BRES = 7,     // ... with the workgroup's weight slice resident in LDS (6 was its stream-K form)
   K_RETIRED = 8,  // a stream-K number kept for old plans: runs FB
   K_P3PATCH = 9,  // plane GEMM, 3x3 / stride 1 with the input patch resident in LDS (conv_p3_patch.h)
 };
@@ -82,10 +81,12 @@ enum GemmKind {
 
 // ---------------------------------------------------------------- plane (fp32) forward / data gradient
 // X(cfg, KIND, WM, WN, TM, TN, KW, NST, OCC, FB): NST ring slots of KW-deep k-slices, built for OCC
-// workgroups per CU. 18-22 persistent twins of per-tile cfgs (FB: the twin), 23-28 stream-K (FB: the
-// whole-tile persistent form; 28 has cfg 8's geometry and no persistent form), 31-36 weights
-// resident. 29 / 30 (stream-K 256x128 / 128x256 of 64x64 wave tiles) are retired -- a 272-byte stack
-// frame, 5x slower (profiles/r6_quantization_streamk.txt) -- and run cfg 10 / 11.
+// workgroups per CU. 18-22 persistent twins of per-tile cfgs (FB: the twin), 31-36 weights resident.
+// 23-30 are the retired stream-K numbers: the form was measured 11-30 % slower per layer than the
+// whole-tile persistent kernels (29 / 30, 64x64 wave tiles: 5x slower) and removed
+// (profiles/r4v_streamk_probe.txt, profiles/r6_quantization_streamk.txt). The rows stay, with their
+// tiles, so that tuned/*.json and autotune caches that name them keep their meaning: each runs FB, the
+// cfg it used to fall back to.
 #define HCB_P3_CFGS(X)                          \
   X(0, TILE, 2, 2, 64, 32, 64, 2, 1, -1)        \
   X(1, TILE, 2, 2, 32, 64, 64, 2, 1, -1)        \
@@ -110,12 +111,12 @@ enum GemmKind {
   X(20, PERSIST, 2, 2, 32, 32, 32, 3, 2, 16)    \
   X(21, PERSIST, 2, 2, 32, 32, 32, 2, 3, 17)    \
   X(22, PERSIST, 2, 4, 64, 32, 32, 3, 1, 7)     \
-  X(23, STREAMK, 2, 2, 32, 64, 32, 2, 2, 18)    \
-  X(24, STREAMK, 2, 2, 64, 32, 32, 2, 2, 19)    \
-  X(25, STREAMK, 2, 2, 32, 32, 32, 3, 2, 20)    \
-  X(26, STREAMK, 2, 2, 32, 32, 32, 2, 3, 21)    \
-  X(27, STREAMK, 2, 4, 64, 32, 32, 3, 1, 22)    \
-  X(28, STREAMK, 4, 2, 32, 64, 32, 3, 1, 8)     \
+  X(23, RETIRED, 2, 2, 32, 64, 32, 2, 2, 18)    \
+  X(24, RETIRED, 2, 2, 64, 32, 32, 2, 2, 19)    \
+  X(25, RETIRED, 2, 2, 32, 32, 32, 3, 2, 20)    \
+  X(26, RETIRED, 2, 2, 32, 32, 32, 2, 3, 21)    \
+  X(27, RETIRED, 2, 4, 64, 32, 32, 3, 1, 22)    \
+  X(28, RETIRED, 4, 2, 32, 64, 32, 3, 1, 8)     \
   X(29, RETIRED, 4, 2, 64, 64, 32, 2, 1, 10)    \
   X(30, RETIRED, 2, 4, 64, 64, 32, 2, 1, 11)    \
   X(31, BRES, 1, 4, 64, 64, 32, 3, 1, 18)       \
@@ -240,10 +241,6 @@ constexpr bool conv_cfg_has_inf(int cfg) { return cfg >= 0 && cfg < N_CONV_CFG &
 constexpr bool p3_cfg_has_inf(int cfg) { return gemm_kind(P3_CFGS, cfg) == K_TILE; }
 // in-launch split-K runs on the LDS-DMA kernels: not on a register-staged row
 constexpr bool conv_cfg_splitk(int cfg) { return cfg >= 0 && gemm_kind(CONV_CFGS, cfg) != K_REG; }
-// the stream-K numbers (retired ones included) take the split-K workspace
-constexpr bool p3_cfg_streamk(int cfg) {
-  return gemm_kind(P3_CFGS, cfg) == K_STREAMK || gemm_kind(P3_CFGS, cfg) == K_RETIRED;
-}
 constexpr bool wp3_cfg_persistent(int cfg) { return gemm_kind(WP3_CFGS, cfg) == K_PERSIST; }
 
 // ---------------------------------------------------------------- the resident 3x3 patch (conv_p3_patch.h)

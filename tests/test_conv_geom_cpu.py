@@ -126,7 +126,7 @@ def specs():
     return out, (st.fold_spec, st.fold_shape)
 
 
-# cfg arguments per path: None, an int, (cfg, splits > 1), a stream-K / patch cfg
+# cfg arguments per path: None, an int, (cfg, splits > 1), a retired / patch cfg
 CFGS = {False: (None, 5, (13, 2), 17), True: (None, 3, (7, 2), (23, 1))}
 WCFGS = {False: (None, (3, 4)), True: (None, (6, 4))}
 

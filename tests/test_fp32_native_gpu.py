@@ -49,8 +49,7 @@ CASES = [(64, 256, 1, 1, 0, 14), (64, 64, 3, 1, 1, 14), (128, 128, 3, 2, 1, 14),
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}x{c[1]}k{c[2]}s{c[3]}")
 @pytest.mark.parametrize("cfg", [None, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22,
-                                 23, 24, 25, 26, 27, 28, 31, 32, 33, 34, 35, 36, (0, 2), (4, 3), (7, 2), (10, 3), (14, 3),
-                                 (16, 5), (17, 6)],
+                                 28, 31, 32, 33, 34, 35, 36, (0, 2), (4, 3), (7, 2), (10, 3), (14, 3), (16, 5), (17, 6)],
                          ids=str)
 def test_fp32_conv_fwd_dgrad_wgrad_match_fp64(fp32_mode, case, cfg):
     """bf16x6 on planes reproduces the fp32 convolution to fp32 accuracy (~1e-6): fwd, data grad
@@ -59,8 +58,9 @@ def test_fp32_conv_fwd_dgrad_wgrad_match_fp64(fp32_mode, case, cfg):
     planes by the ops themselves. cfg 7-13: 32-deep slots (64-byte LDS rows) and 128x128 / 256x128
     block tiles; (cfg, S): in-launch split-K (fixed-order slab sum); weight-grad cfg 6-11: 32-deep slots, up to 256x128 / 128x256; fwd cfg 14-17 / weight-grad 12-15: two or
     three workgroups per CU; 18-22: the persistent short-K kernel (conv_p3_persist.h; the strided
-    data gradients' remap form runs its twin); 23-27: its stream-K form; 31-34: its weights-resident
-    form (falling back where it does not fit)."""
+    data gradients' remap form runs its twin); 31-36: its weights-resident form (falling back where it
+    does not fit); 28: a retired stream-K number, which runs cfg 8 (the other retired numbers, whose
+    fallbacks 18-22 are in this list: test_retired_p3_cfgs_run_their_fallback)."""
     cin, cout, k, s, pad, H = case
     spec, p, pk, ps = _conv(cin, cout, k, s, pad)
     assert Fn.lo_pack(pk.pack) is not None and Fn.lo_pack(pk.tr) is not None
@@ -133,11 +133,9 @@ def test_fp32_persistent_short_k_gemm(fp32_mode, cfg, shape):
     and column tails (2645 rows, 96 outputs against 64 / 128-wide tiles), a 3x3 (18 k-steps); the
     register epilogue's output, ReLU and BN statistics (shifted sums in STAT_R replicas) against
     fp64, and the deterministic mode's one-replica-per-64-rows statistics bitwise reproducible.
-    cfg 23-27: the stream-K form -- equal (tile, k-step) shares per workgroup, split tiles summed
-    through the workspace (256x256 3x3 at 14 x 14 x 4: 14 tiles x 72 k-steps over the grid, up to
-    ~20 shares per tile), bitwise reproducible output and statistics. cfg 31-36: each workgroup's
-    weight slice resident in LDS (one or several N tiles: 40 / 64 / 96 / 256 outputs, K = 64 / 256),
-    the others falling back."""
+    cfg 23-28: retired stream-K numbers, which run their fallbacks (18-22 and 8). cfg 31-36: each
+    workgroup's weight slice resident in LDS (one or several N tiles: 40 / 64 / 96 / 256 outputs,
+    K = 64 / 256), the others falling back."""
     cin, cout, k, H, N = shape
     pad = k // 2
     spec, p, pk, ps = _conv(cin, cout, k, 1, pad)
@@ -178,6 +176,41 @@ def test_fp32_persistent_short_k_gemm(fp32_mode, cfg, shape):
         Fn.conv_forward(x, spec, pk.pack, p.data, y2, stats=a, stats_R=Rd, cfg=cfg, stats_shift=shift)
         runs.append((a, y2.clone()))
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+
+
+# plane cfg 23-30 -> FB of their gemm_cfg.h rows
+RETIRED_FB = {23: 18, 24: 19, 25: 20, 26: 21, 27: 22, 28: 8, 29: 10, 30: 11}
+
+
+@pytest.fixture(scope="module")
+def retired_case():
+    """One 1x1 problem with row and column tails (2645 rows, 96 outputs against 64 / 128-wide tiles)
+    and its fp64 reference, shared by every retired number."""
+    cin, cout, k, H, N = 256, 96, 1, 23, 5
+    spec, p, pk, ps = _conv(cin, cout, k, 1, 0)
+    torch.manual_seed(4)
+    x = torch.randn(N, H, H, cin, device=DEV)
+    ref = torch.nn.functional.conv2d(x.double().cpu().permute(0, 3, 1, 2), p.data.double().cpu().permute(0, 3, 1, 2))
+    shift = (torch.randn(cout) * 0.1).to(DEV)
+    return spec, p, pk, ps, x, ref.permute(0, 2, 3, 1), shift
+
+
+@pytest.mark.parametrize("cfg", sorted(RETIRED_FB))
+def test_retired_p3_cfgs_run_their_fallback(fp32_mode, retired_case, cfg):
+    """cfg 23-30 were the stream-K kernels' numbers (removed: profiles/retire_streamk.txt). A plan that
+    still names one runs the row's fallback cfg: output and BN statistics bitwise equal to that cfg's,
+    and the output against fp64 within the file's bound."""
+    spec, p, pk, ps, x, ref, shift = retired_case
+    N, H, _, cout = ref.shape
+    Rd = Fn.det_replicas(N * H * H)
+    out = []
+    for c in (cfg, RETIRED_FB[cfg]):
+        y = torch.full((N, H, H, cout), float("nan"), device=DEV)
+        st = torch.zeros(Rd * 2 * cout, device=DEV)
+        Fn.conv_forward(x, spec, pk.pack, p.data, y, stats=st, stats_R=Rd, cfg=c, stats_shift=shift)
+        out.append((y, st))
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+    assert rel_err(out[0][0], ref) < 3e-6
 
 
 @pytest.mark.parametrize("C", [64, 256, 2048])
@@ -405,12 +438,12 @@ def test_fp32_fused_bn_backward_matches_unfused(fp32_mode, case, mode):
     assert rel_err(a[0], s1) < 1e-5 and rel_err(a[1], s2) < 1e-5
 
 
-@pytest.mark.parametrize("cfg", [18, 19, 20, 21, 22, 23])
+@pytest.mark.parametrize("cfg", [18, 19, 20, 21, 22])
 @pytest.mark.parametrize("case", [(96, 64, 1, 23, 5, False), (64, 64, 3, 30, 3, True), (256, 128, 1, 14, 4, True)],
                          ids=lambda c: f"{c[0]}x{c[1]}k{c[2]}H{c[3]}N{c[4]}acc{int(c[5])}")
 def test_fp32_persistent_fused_bn_backward(fp32_mode, cfg, case):
     """The persistent plane GEMM's BNB register epilogue (conv_p3_persist.h, a fused BN-backward data
-    gradient walking several tiles per workgroup; cfg 23 -- stream-K -- falls back to it): g for
+    gradient walking several tiles per workgroup): g for
     modes 0 / 1 / 2 with and without the beta source, row tails (2645 rows) and a 96-column tail,
     sum(g) / sum(g * xhat) against fp64, and the deterministic replicas bitwise reproducible."""
     cin, cout, k, H, N, accumulate = case
@@ -432,28 +465,30 @@ def test_fp32_persistent_fused_bn_backward(fp32_mode, cfg, case):
     M = N * H * H
     xh = ((z.double() - mean.double()) * invstd.double()).cpu()
     Fn.set_p3p_bnb(2)  # every mode on the persistent kernel (the default, 0, runs the twin)
-    for mode in (0, 1, 2):
-        g = ref + (base.double().cpu() if accumulate else 0)
-        if mode == 1:
-            g = g * (yf.cpu() > 0).double()
-        elif mode == 2:
-            g = g * ((xh * gamma.double().cpu() + beta.double().cpu()) > 0).double()
-        R = 8
-        acc = torch.zeros(R, 2, cin, device=DEV)
-        dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
-        bnb = Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, mode, acc, R)
-        Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1), bnb=bnb)
-        assert rel_err(dx, g) < 3e-6, mode
-        a = acc.double().sum(0).cpu()
-        assert rel_err(a[0], g.reshape(-1, cin).sum(0)) < 1e-5, mode
-        assert rel_err(a[1], (g.reshape(-1, cin) * xh.reshape(-1, cin)).sum(0)) < 1e-5, mode
-    Rd = Fn.det_replicas(M)
-    runs = []
-    for _ in range(2):
-        a = torch.zeros(Rd, 2, cin, device=DEV)
-        dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
-        Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1),
-                      bnb=Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, 2, a, Rd))
-        runs.append((a, dx))
-    Fn.set_p3p_bnb(0)
-    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+    try:
+        for mode in (0, 1, 2):
+            g = ref + (base.double().cpu() if accumulate else 0)
+            if mode == 1:
+                g = g * (yf.cpu() > 0).double()
+            elif mode == 2:
+                g = g * ((xh * gamma.double().cpu() + beta.double().cpu()) > 0).double()
+            R = 8
+            acc = torch.zeros(R, 2, cin, device=DEV)
+            dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
+            bnb = Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, mode, acc, R)
+            Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1), bnb=bnb)
+            assert rel_err(dx, g) < 3e-6, mode
+            a = acc.double().sum(0).cpu()
+            assert rel_err(a[0], g.reshape(-1, cin).sum(0)) < 1e-5, mode
+            assert rel_err(a[1], (g.reshape(-1, cin) * xh.reshape(-1, cin)).sum(0)) < 1e-5, mode
+        Rd = Fn.det_replicas(M)
+        runs = []
+        for _ in range(2):
+            a = torch.zeros(Rd, 2, cin, device=DEV)
+            dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
+            Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1),
+                          bnb=Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, 2, a, Rd))
+            runs.append((a, dx))
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+    finally:
+        Fn.set_p3p_bnb(0)

@@ -11,8 +11,9 @@ from azure_hc_intel_tf_amd.ops import functional as Fn
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "azure_hc_intel_tf_amd")
 BUILDS = [("_hcb_kernels.so", "hcb"), ("_hcb_kernels_f16.so", "hcb16")]
 COLS = ("cfg", "kind", "wm", "wn", "tm", "tn", "kw", "nst", "occ", "extra", "fb", "inf")
-# launcher kinds (gemm_cfg.h GemmKind)
-REG, GLDS, PATCH, KQ, TILE, PERSIST, STREAMK, BRES, RETIRED = range(9)
+# launcher kinds (gemm_cfg.h GemmKind; 6 was the stream-K kernels' and stays unused)
+REG, GLDS, PATCH, KQ, TILE, PERSIST = range(6)
+BRES, RETIRED = 7, 8
 
 # Every row of every family, (kind, WM, WN, TM, TN, slot depth, ring slots, occupancy, PMAX / KS, fallback),
 # as the launch switches of the commit before the tables spelled them. A cfg number stored in
@@ -58,10 +59,10 @@ PINNED = {
         18: (PERSIST, 2, 2, 32, 64, 32, 2, 2, 0, 15), 19: (PERSIST, 2, 2, 64, 32, 32, 2, 2, 0, 14),
         20: (PERSIST, 2, 2, 32, 32, 32, 3, 2, 0, 16), 21: (PERSIST, 2, 2, 32, 32, 32, 2, 3, 0, 17),
         22: (PERSIST, 2, 4, 64, 32, 32, 3, 1, 0, 7),
-        23: (STREAMK, 2, 2, 32, 64, 32, 2, 2, 0, 18), 24: (STREAMK, 2, 2, 64, 32, 32, 2, 2, 0, 19),
-        25: (STREAMK, 2, 2, 32, 32, 32, 3, 2, 0, 20), 26: (STREAMK, 2, 2, 32, 32, 32, 2, 3, 0, 21),
-        27: (STREAMK, 2, 4, 64, 32, 32, 3, 1, 0, 22), 28: (STREAMK, 4, 2, 32, 64, 32, 3, 1, 0, 8),
-        # retired: no kernel of their own; the geometry of the cfgs they run (256x128 / 128x256 tiles)
+        # retired (the stream-K numbers): no kernel of their own; the geometry of the cfgs they run
+        23: (RETIRED, 2, 2, 32, 64, 32, 2, 2, 0, 18), 24: (RETIRED, 2, 2, 64, 32, 32, 2, 2, 0, 19),
+        25: (RETIRED, 2, 2, 32, 32, 32, 3, 2, 0, 20), 26: (RETIRED, 2, 2, 32, 32, 32, 2, 3, 0, 21),
+        27: (RETIRED, 2, 4, 64, 32, 32, 3, 1, 0, 22), 28: (RETIRED, 4, 2, 32, 64, 32, 3, 1, 0, 8),
         29: (RETIRED, 4, 2, 64, 64, 32, 2, 1, 0, 10), 30: (RETIRED, 2, 4, 64, 64, 32, 2, 1, 0, 11),
         31: (BRES, 1, 4, 64, 64, 32, 3, 1, 0, 18), 32: (BRES, 2, 4, 64, 64, 32, 2, 1, 0, 18),
         33: (BRES, 2, 2, 32, 32, 32, 3, 1, 0, 20), 34: (BRES, 2, 2, 64, 32, 32, 2, 1, 0, 19),
@@ -113,14 +114,15 @@ def test_python_tile_tables_equal_the_exported_tiles(tables):
     assert Fn._WP3_TILES == _tiles(tables["wgrad_p3"])
     p3 = _tiles(tables["p3"])
     retired = {c for c, r in tables["p3"].items() if r["kind"] == RETIRED}
-    assert retired == {29, 30} and not retired & set(Fn._P3_TILES)
+    assert retired == set(range(23, 31)) and not retired & set(Fn._P3_TILES)
     assert Fn._P3_TILES == {c: t for c, t in p3.items() if c not in retired}
     assert Fn.PATCH_CFGS == tuple(c for c, r in tables["conv"].items() if r["kind"] == PATCH)
     assert Fn.PATCH_CFG0 == min(Fn.PATCH_CFGS)
 
 
 def test_occupancy_and_resident_ring_slots(tables):
-    assert Fn._P3_OCC == {c: r["occ"] for c, r in tables["p3"].items() if r["occ"] != 1}
+    # (a retired row keeps the columns of the kernel it had; the planner lists launchable cfgs only)
+    assert Fn._P3_OCC == {c: r["occ"] for c, r in tables["p3"].items() if r["occ"] != 1 and r["kind"] != RETIRED}
     assert Fn._WP3_OCC == {c: r["occ"] for c, r in tables["wgrad_p3"].items() if r["occ"] != 1}
     assert Fn._P3_BRES == {c: r["nst"] for c, r in tables["p3"].items() if r["kind"] == BRES}
 
@@ -129,7 +131,6 @@ def test_fallbacks(tables):
     conv, p3 = tables["conv"], tables["p3"]
     assert Fn._PATCH_TWIN == {c: r["fb"] for c, r in conv.items() if r["kind"] == PATCH}
     assert all((r["fb"] >= 0) == (r["kind"] == PATCH) for r in conv.values())
-    assert Fn._P3_STREAMK == {c: r["fb"] for c, r in p3.items() if r["kind"] == STREAMK}
 
     def per_tile(c):
         while p3[c]["kind"] != TILE:
@@ -138,7 +139,8 @@ def test_fallbacks(tables):
 
     assert all((r["fb"] >= 0) == (r["kind"] != TILE) for r in p3.values())
     assert Fn._P3_PERSIST == {c: per_tile(c) for c, r in p3.items() if r["kind"] not in (TILE, RETIRED)}
-    assert {c: per_tile(c) for c, r in p3.items() if r["kind"] == RETIRED} == {29: 10, 30: 11}
+    retired = {c: per_tile(c) for c, r in p3.items() if r["kind"] == RETIRED}
+    assert retired == {23: 15, 24: 14, 25: 16, 26: 17, 27: 7, 28: 8, 29: 10, 30: 11} == Fn._P3_RETIRED
     # a patch twin keeps the row tile, so a per-tile statistics slab keeps its size
     assert all(r["wm"] * r["tm"] == conv[r["fb"]]["wm"] * conv[r["fb"]]["tm"] for r in conv.values() if r["fb"] >= 0)
     assert all(r["fb"] == -1 for fam in ("wgrad", "wgrad_p3") for r in tables[fam].values())

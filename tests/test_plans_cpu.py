@@ -72,15 +72,21 @@ def test_learning_rate_written_only_when_it_moves():
     assert t._lr_dev == 0.05
 
 
-def test_streamk_cfgs_share_the_persistent_tiles():
-    """cfg 23-27 are the stream-K form of the persistent cfg 18-22: same tiles / occupancy, no
-    split-K candidates of their own, and a plan that needs the split-K workspace."""
-    for sk, pc in Fn._P3_STREAMK.items():
-        assert Fn._P3_TILES[sk] == Fn._P3_TILES[pc] and Fn._P3_OCC.get(sk, 1) == Fn._P3_OCC.get(pc, 1)
-        assert Fn._P3_PERSIST[sk] == Fn._P3_PERSIST.get(pc, pc)
-    cands = Fn.p3_candidates(12544, 256, 2304)
-    assert {27} <= {c for c, _ in cands}
-    assert all(s == 1 for c, s in cands if c in Fn._P3_STREAMK)
+def test_retired_cfgs_are_not_offered_and_pass_through(monkeypatch):
+    """cfg 23-30 (the removed stream-K kernels' numbers) are in no candidate list, and an explicit or
+    tuned plan that names one passes through unchanged -- the launcher runs its fallback -- without
+    asking for the split-K workspace."""
+    retired = set(range(23, 31))
+    for shape in ((12544, 256, 2304), (200704, 256, 64)):
+        assert not retired & {c for c, _ in Fn.p3_candidates(*shape)}
+
+    def no_workspace(device):
+        raise AssertionError("a retired cfg with one split needs no split-K workspace")
+
+    monkeypatch.setattr(Fn, "ensure_splitk_workspace", no_workspace)
+    assert Fn._plan((27, 1), 12544, 256, 2304, torch.device("cpu"), 9, **Fn._P3_PLAN) == (27, 1)
+    monkeypatch.setitem(Fn._tuned, Fn.fwd3_key(12544, 256, 2304, 9), (27, 1))
+    assert Fn._plan(None, 12544, 256, 2304, torch.device("cpu"), 9, **Fn._P3_PLAN) == (27, 1)
 
 
 def test_b_resident_cfgs_only_where_the_weights_fit():

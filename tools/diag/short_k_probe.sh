@@ -3,7 +3,7 @@
 # tile family, isolated (tools/layer_probe.py --fp32)
 set -o pipefail
 mkdir -p gpurun_out/r6v
-for c in 17 21 16 20 15 18 14 19 7 22 8 13 27; do
+for c in 17 21 16 20 15 18 14 19 7 22 8 13; do
   timeout -k 10 60 python tools/layer_probe.py --fp32 --layer stage3/block2/conv3 --op fwd --cfg $c --reps 40 2>&1 \
     | grep -v amdgpu.ids >> gpurun_out/r6v/sk.txt || exit 1
 done
