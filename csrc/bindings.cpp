@@ -253,11 +253,6 @@ void set_splitk_workspace(const Tensor& ws, const Tensor& cnt) {
   g_splitk_cnt_n = cnt.numel();
 }
 
-void set_p3p_bnb(int64_t v) {
-  TORCH_CHECK(v >= 0 && v <= 2, "hcb.set_p3p_bnb: 0, 1 or 2");
-  hcb::set_p3p_bnb((int)v);
-}
-
 const float* opt_f32(const c10::optional<Tensor>& t, int64_t n, const char* what) {
   if (!t.has_value()) return nullptr;
   check_f32(*t, what);
@@ -1770,7 +1765,6 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("p3_patch_fit(int cfg, int H, int W, bool bnb) -> int[]", p3_patch_fit);
   m.def("conv_geom_fields(str kind) -> str[]", conv_geom_fields);
   m.def("set_splitk_workspace(Tensor ws, Tensor cnt) -> ()");
-  m.def("set_p3p_bnb(int v) -> ()", set_p3p_bnb);
   m.def("conv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int[] geom, int cfg, int splits) -> ()");
   m.def("bn_apply(Tensor x, int ldx, Tensor(a!) y, int ldy, Tensor? res, int ldr, int M, int C, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, int relu, float? act_max=None) -> ()");
   m.def("pool_fwd(Tensor x, Tensor(a!) y, Tensor(b!)? idx, int[] geom) -> ()");

@@ -33,9 +33,9 @@ namespace hcb {
 // -1: launched.
 #define HCB_CASE_TILE(...)
 #define HCB_CASE_PERSIST(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
-  case C: return launch_p3p<WM, WN, TM, TN, KW, NST, OCC>(p, st) ? -1 : launch_p3_persist(p, FB, st);
+  case C: return launch_p3p<WM, WN, TM, TN, KW, NST, OCC, false>(p, st) ? -1 : launch_p3_persist(p, FB, st);
 #define HCB_CASE_BRES(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
-  case C: return launch_p3bres<WM, WN, TM, TN, KW, NST>(p, st) ? -1 : launch_p3_persist(p, FB, st);
+  case C: return launch_p3p<WM, WN, TM, TN, KW, NST, OCC, true>(p, st) ? -1 : launch_p3_persist(p, FB, st);
 #define HCB_CASE_RETIRED(C, WM, WN, TM, TN, KW, NST, OCC, FB) \
   case C: return launch_p3_persist(p, FB, st);
 static int launch_p3_persist(const ConvParams& p, int cfg, hipStream_t st) {
@@ -48,8 +48,6 @@ static int launch_p3_persist(const ConvParams& p, int cfg, hipStream_t st) {
 #undef HCB_CASE_PERSIST
 #undef HCB_CASE_BRES
 #undef HCB_CASE_RETIRED
-
-void set_p3p_bnb(int v) { p3p_bnb_level() = v; }
 
 void launch_conv_p3(const ConvParams& p, int cfg, hipStream_t st) {
   if (p.inf) {  // the inference epilogue: per-tile kernels only (checked by the binding)

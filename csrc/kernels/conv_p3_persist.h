@@ -26,7 +26,7 @@
 // The reference's role: the MKL-DNN fp32 Conv2D forward primitive, driven by
 // /root/reference/benchmark-scripts/run-tf-sing-ucx-openmpi.sh:62-81.
 #pragma once
-#include <cstdlib>
+#include <climits>
 
 #include "conv_p3_fwd.h"
 #include "conv_p3_wgrad.h"
@@ -51,35 +51,25 @@ constexpr size_t p3p_ring_bytes() {
 // two fp32 adds commute exactly, so the deterministic mode's one-replica-per-64-rows statistics stay
 // bitwise reproducible.
 //
-// BNB (a data gradient whose output is a BN layer's dy, conv_p3_fwd.h's fused BN-backward epilogue
-// from the registers): per tile, z (fp32), the ReLU-mask source (mode 1: the bf16 hi plane of y) and
-// the beta-accumulate source (fp32) of the lane's accumulator elements are loaded in two chunks of
-// wave rows (one memory round trip each), g = (acc [+ beta]) gated, stored fp32, and sum(g) /
-// sum(g * xhat) reduced per column by shuffles into one buffer atomic per column and wave (replica =
-// the wave's 64-row block, as the statistics) -- EOPS vector-memory instructions after the loads.
-//
 // BRES (B resident, cfg 31-36): the workgroup's whole weight slice (its N tile's every k-step: three
 // plane images, nk * 3 * BN * 64 B) is DMA'd into LDS once, and the ring streams A only. The host
 // sizes the grid as a multiple of the N-tile count, so first, first + grid, ... all lie in the N tile
 // first % tiles_n. For the 1x1 GEMMs with K <= 256 the weight tile is as large as the activation
 // tile or larger (stage 1, 64 -> 256: BN x K = 256 x 64 against BM x K = 64 x 64), so re-staging it
 // for every tile doubled-to-quintupled the L2 -> LDS operand traffic that bounds these launches.
-template <int WM, int WN, int TM, int TN, int KW, int NST, bool CBIG, bool STATS, int OCC, bool BNB = false,
-          bool BRES = false>
+template <int WM, int WN, int TM, int TN, int KW, int NST, bool CBIG, bool STATS, int OCC, bool BRES = false>
 __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_p3_persist_kernel(ConvParams p) {
   constexpr int BM = WM * TM, BN = WN * TN;
   constexpr int MI = TM / 16, NI = TN / 16;
   constexpr int NT = WM * WN * 64, CPR = KW / 8, RB = KW * 2;
   constexpr int RP = NT / CPR;
   constexpr int AV = BM / RP, BV = BN / RP;
-  static_assert(!(BRES && BNB), "B-resident: the forward form");
   constexpr int LOADS = NPL * (AV + (BRES ? 0 : BV));
   constexpr int AIMG = BM * RB, BIMG = BN * RB;
   constexpr int STAGE = BRES ? NPL * AIMG : (int)p3_stage_bytes<BM, BN, KW>();
   // epilogue vector-memory instructions; EDRAIN (64 x 64 wave tiles: more than the vmcnt field can
   // count beside the ring): the epilogue drains itself instead and the ring's waits count 0 for it
-  static_assert(!(STATS && BNB), "a data gradient has no forward statistics");
-  constexpr int EOPS_N = MI * NI * 4 + (STATS || BNB ? 2 * NI : 0);
+  constexpr int EOPS_N = MI * NI * 4 + (STATS ? 2 * NI : 0);
   constexpr bool EDRAIN = LOADS * (NST - 1) + EOPS_N > 63;
   constexpr int EOPS = EDRAIN ? 0 : EOPS_N;
   static_assert(TM >= 32, "at most two adds per statistics slot and tile (deterministic mode)");
@@ -114,13 +104,7 @@ __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_p3_persist_
   const __amdgpu_buffer_rsrc_t wr1 = make_rsrc(p.w_lo, p.w_bytes);
   const __amdgpu_buffer_rsrc_t wr2 = make_rsrc(p.w_lo2, p.w_bytes);
   const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y, (uint32_t)((size_t)p.M * p.ldy * 4));
-  const __amdgpu_buffer_rsrc_t sr = BNB ? make_rsrc(p.bnb_acc, (uint32_t)((size_t)p.bnb_R * 2 * p.Nout * 4))
-                                       : make_rsrc(p.stats, STATS ? (uint32_t)((size_t)p.stats_R * 2 * p.Nout * 4) : 0u);
-  // BNB operands: z and the beta source fp32 (row strides bnb_ld / ldy), y's hi plane bf16 (bnb_ld)
-  const __amdgpu_buffer_rsrc_t zr = make_rsrc(BNB ? p.bnb_z : p.y, BNB ? (uint32_t)((size_t)p.M * p.bnb_ld * 4) : 0u);
-  const __amdgpu_buffer_rsrc_t br = make_rsrc(BNB && p.beta ? p.yres : p.y, BNB && p.beta ? (uint32_t)((size_t)p.M * p.ldy * 4) : 0u);
-  const __amdgpu_buffer_rsrc_t mr = make_rsrc(BNB && p.bnb_mode == 1 ? p.bnb_y : p.y,
-                                              BNB && p.bnb_mode == 1 ? (uint32_t)((size_t)p.M * p.bnb_ld * 2) : 0u);
+  const __amdgpu_buffer_rsrc_t sr = make_rsrc(p.stats, STATS ? (uint32_t)((size_t)p.stats_R * 2 * p.Nout * 4) : 0u);
 
   if constexpr (STATS) {  // published by the first barrier; older than every DMA (vmcnt order)
     for (int c = tid; c < p.Nout; c += NT) ktab[c] = p.stats_shift != nullptr ? p.stats_shift[c] : 0.f;
@@ -185,87 +169,6 @@ __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_p3_persist_
     const int tm = t / tiles_n, tn = t - tm * tiles_n;
     const int rbase = tm * BM + wm * TM;           // the wave's first row
     const int cbase = tn * BN + wn * TN + frow;    // the lane's column in fragment j = 0
-    if constexpr (BNB) {
-      float mu[NI], is[NI], sc[NI], sh[NI], s1[NI], s2[NI];
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int col = cbase + j * 16;
-        const bool cok = col < p.Nout;
-        mu[j] = cok ? p.bnb_mean[col] : 0.f;
-        is[j] = cok ? p.bnb_invstd[col] : 0.f;
-        sc[j] = (cok ? p.bnb_gamma[col] : 0.f) * is[j];
-        sh[j] = (cok ? p.bnb_beta[col] : 0.f) - mu[j] * sc[j];
-        s1[j] = 0.f;
-        s2[j] = 0.f;
-      }
-      const int mode = p.bnb_mode;
-      const bool beta = p.beta != 0;
-      constexpr int HC = MI > 1 ? MI / 2 : 1;  // wave-row fragments per chunk
-#pragma unroll
-      for (int c0 = 0; c0 < MI; c0 += HC) {
-        float zf[HC][4][NI], rf[HC][4][NI];
-        uint32_t yb[HC][4][NI];
-#pragma unroll
-        for (int ii = 0; ii < HC; ++ii)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int row = rbase + (c0 + ii) * 16 + fq * 4 + e;
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-              const int col = cbase + j * 16;
-              const bool ok = (row < p.M) & (col < p.Nout);
-              zf[ii][e][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                  zr, ok ? (uint32_t)(row * p.bnb_ld + col) * 4u : HCB_OOB, 0, 0));
-              rf[ii][e][j] = beta ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                                        br, ok ? (uint32_t)(row * p.ldy + col) * 4u : HCB_OOB, 0, 0))
-                                  : 0.f;
-              yb[ii][e][j] = mode == 1 ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(
-                                             mr, ok ? (uint32_t)(row * p.bnb_ld + col) * 2u : HCB_OOB, 0, 0)
-                                       : 0u;
-            }
-          }
-#pragma unroll
-        for (int ii = 0; ii < HC; ++ii)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int row = rbase + (c0 + ii) * 16 + fq * 4 + e;
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-              const int col = cbase + j * 16;
-              const bool ok = (row < p.M) & (col < p.Nout);
-              const float z = zf[ii][e][j];
-              float g = acc[c0 + ii][j][e] + rf[ii][e][j];
-              if (mode == 1)
-                g = __uint_as_float(yb[ii][e][j] << 16) > 0.f ? g : 0.f;  // the hi plane: > 0 exactly when y > 0
-              else if (mode == 2)
-                g = (z * sc[j] + sh[j]) > 0.f ? g : 0.f;
-              g = ok ? g : 0.f;
-              s1[j] += g;
-              s2[j] += g * ((z - mu[j]) * is[j]);
-              buf_store_f32(yr, ok ? (uint32_t)(row * p.ldy + col) * 4u : HCB_OOB, g);
-            }
-          }
-      }
-      const uint32_t rep = (uint32_t)((rbase >> 6) % p.bnb_R) * 2u * (uint32_t)p.Nout;
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        float a = s1[j], b = s2[j];
-        a += __shfl_xor(a, 16, 64);
-        b += __shfl_xor(b, 16, 64);
-        a += __shfl_xor(a, 32, 64);
-        b += __shfl_xor(b, 32, 64);
-        const int col = cbase + j * 16;
-        const bool own = (fq == 0) & (col < p.Nout);
-        buf_atomic_add_f32(sr, own ? (rep + (uint32_t)col) * 4u : HCB_OOB, a);
-        buf_atomic_add_f32(sr, own ? (rep + (uint32_t)(p.Nout + col)) * 4u : HCB_OOB, b);
-      }
-      if constexpr (EDRAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int ii = 0; ii < MI; ++ii)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[ii][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      return;
-    }
     if constexpr (STATS) {
       const int wrows = p.M - rbase;
       const uint32_t rep = (uint32_t)((rbase >> 6) % p.stats_R) * 2u * (uint32_t)p.Nout;
@@ -412,15 +315,6 @@ __global__ __launch_bounds__(WM* WN * 64, OCC* WM* WN / 4) void conv_p3_persist_
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dummy pieces have landed before the LDS is freed
 }
 
-// kernels.h set_p3p_bnb
-inline int& p3p_bnb_level() {
-  static int v = [] {
-    const char* e = std::getenv("HCB_P3P_BNB");
-    return e != nullptr ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
 // the device's CU count (256 when the runtime does not say): the persistent launchers size their
 // grids by it
 inline int p3p_cus() {
@@ -434,102 +328,52 @@ inline int p3p_cus() {
   return cus;
 }
 
-// cfg 18-22 (persistent twins of cfg 15, 14, 16, 17, 7): false when the problem needs an epilogue
-// feature this kernel does not have (the caller then launches the twin). A fused BN-backward data
-// gradient (bnb_acc) runs the BNB instantiation.
-template <int WM, int WN, int TM, int TN, int KW, int NST, int OCC>
-static bool launch_p3p(const ConvParams& p, hipStream_t st) {
-  constexpr int BM = WM * TM, BN = WN * TN;
-  const bool stats = p.stats != nullptr;
-  const int nk = p.Kpad / KW;
-  const size_t ring = p3p_ring_bytes<BM, BN, KW, NST>();
-  const size_t lds = ring + (stats ? (size_t)p.Nout * 4 : 0);
-  const bool bnb = p.bnb_acc != nullptr;
-  // the mode-1 mask is a 2-byte load per accumulator element (the hi plane of y): measured slower
-  // than the twin's vector prefetch, so only p3p_bnb_level() 2 runs it here
-  if ((bnb && (p3p_bnb_level() == 0 || (p.bnb_mode == 1 && p3p_bnb_level() < 2))) || p.remap || p.idil_h > 1 || p.idil_w > 1 || p.splits != 1 || (p.beta && !bnb) ||
-      p.bias != nullptr || !p.out_f32 || (bnb && (stats || p.bnb_R <= 0 || p.bnb_mode < 0 || p.bnb_mode > 2)) ||
-      (stats && p.stats_R <= 0) || nk < NST - 1 || p.Kpad % KW != 0 || lds > 160 * 1024 ||
-      (size_t)p.M * p.ldy * 4 >= (1ull << 31) || (bnb && (size_t)p.M * p.bnb_ld * 4 >= (1ull << 31)))
-    return false;
-  const bool cbig = (p.C % KW) == 0;
-  static bool once = false;
-  if (!once) {
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, true>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, true>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC>);
-    once = true;
-  }
-  const int cus = p3p_cus();
-  const int ntiles = ((p.M + BM - 1) / BM) * ((p.Nout + BN - 1) / BN);
-  const int per_cu = (int)((160 * 1024) / lds) < OCC ? (int)((160 * 1024) / lds) : OCC;
-  const int slots = cus * (per_cu > 0 ? per_cu : 1);
-  const int grid = ntiles < slots ? ntiles : slots;
-  const dim3 b(WM * WN * 64);
-  if (bnb && cbig)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, true>), dim3(grid), b,
-                       lds, st, p);
-  else if (bnb)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, true>), dim3(grid),
-                       b, lds, st, p);
-  else if (cbig && stats)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC>), dim3(grid), b, lds, st, p);
-  else if (cbig)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC>), dim3(grid), b, lds, st, p);
-  else if (stats)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC>), dim3(grid), b, lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC>), dim3(grid), b, lds, st,
-                       p);
-  return true;
+// the persistent launchers' grid: one workgroup per resident slot -- a CU holds 160 KB / lds of them,
+// at most `cap`, at least one -- and never more than the work items; rounded down to a multiple of
+// `unit` (BRES: the N-tile count)
+inline int p3p_grid(int items, size_t lds, int cap, int unit = 1) {
+  const int fit = (int)((160 * 1024) / lds);
+  const int per_cu = fit < cap ? fit : cap;
+  const int slots = p3p_cus() * (per_cu > 0 ? per_cu : 1);
+  return ((items < slots ? items : slots) / unit) * unit;
 }
 
-// cfg 31-34: the B-resident form (BRES above). False when the problem does not fit it (more than one
-// N tile, the weights + ring over the LDS, an epilogue feature the persistent kernel lacks): the
-// caller then runs the whole-tile persistent cfg.
-template <int WM, int WN, int TM, int TN, int KW, int NST>
-static bool launch_p3bres(const ConvParams& p, hipStream_t st) {
-  constexpr int BM = WM * TM, BN = WN * TN, NPLc = NPL;
+// cfg 18-22 (persistent twins of cfg 15, 14, 16, 17, 7) and, BRES, cfg 31-36 (the B-resident form:
+// the ring holds A only, every k-step's weight images follow it). False when the problem needs an
+// epilogue feature this kernel does not have (a fused BN backward among them) or does not fit it
+// (the LDS; BRES: fewer resident workgroups than N tiles): the caller then runs the row's fallback.
+// The whole-tile rows fill at most OCC workgroups per CU, the B-resident ones as many as the LDS holds.
+template <int WM, int WN, int TM, int TN, int KW, int NST, int OCC, bool BRES>
+static bool launch_p3p(const ConvParams& p, hipStream_t st) {
+  constexpr int BM = WM * TM, BN = WN * TN;
+  static_assert(!BRES || OCC == 1, "the B-resident rows are built with OCC 1");
   const bool stats = p.stats != nullptr;
   const int nk = p.Kpad / KW;
-  const size_t lds = (size_t)NST * NPLc * BM * KW * 2 + (size_t)nk * NPLc * BN * KW * 2 + (stats ? (size_t)p.Nout * 4 : 0);
+  const size_t ring = BRES ? (size_t)NPL * KW * 2 * (NST * BM + nk * BN) : p3p_ring_bytes<BM, BN, KW, NST>();
+  const size_t lds = ring + (stats ? (size_t)p.Nout * 4 : 0);
   if (p.bnb_acc != nullptr || p.remap || p.idil_h > 1 || p.idil_w > 1 || p.splits != 1 || p.beta ||
       p.bias != nullptr || !p.out_f32 || (stats && p.stats_R <= 0) || nk < NST - 1 || p.Kpad % KW != 0 ||
       lds > 160 * 1024 || (size_t)p.M * p.ldy * 4 >= (1ull << 31))
     return false;
-  const bool cbig = (p.C % KW) == 0;
-  static bool once = false;
-  if (!once) {
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, 1, false, true>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, 1, false, true>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, 1, false, true>);
-    (void)set_lds_max(conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, 1, false, true>);
-    once = true;
-  }
-  const int cus = p3p_cus();
   const int tiles_n = (p.Nout + BN - 1) / BN;
   const int ntiles = ((p.M + BM - 1) / BM) * tiles_n;
-  const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
-  const int slots = cus * per_cu;
-  // a multiple of the N-tile count: each workgroup's tiles share one N tile (its resident slice)
-  const int grid = ((ntiles < slots ? ntiles : slots) / tiles_n) * tiles_n;
+  // BRES, a multiple of the N-tile count: each workgroup's tiles share one N tile (its resident slice)
+  const int grid = BRES ? p3p_grid(ntiles, lds, INT_MAX, tiles_n) : p3p_grid(ntiles, lds, OCC);
   if (grid <= 0) return false;
-  const dim3 b(WM * WN * 64);
-  if (cbig && stats)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, 1, false, true>), dim3(grid),
-                       b, lds, st, p);
-  else if (cbig)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, 1, false, true>), dim3(grid),
-                       b, lds, st, p);
-  else if (stats)
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, 1, false, true>), dim3(grid),
-                       b, lds, st, p);
-  else
-    hipLaunchKernelGGL((conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, 1, false, true>), dim3(grid),
-                       b, lds, st, p);
+  // the instantiations [CBIG][STATS]; the LDS limit of all four is raised at the row's first launch
+  using Kern = void (*)(ConvParams);
+  static const Kern kern[2][2] = {{conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, false, OCC, BRES>,
+                                   conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, false, true, OCC, BRES>},
+                                  {conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, false, OCC, BRES>,
+                                   conv_p3_persist_kernel<WM, WN, TM, TN, KW, NST, true, true, OCC, BRES>}};
+  static bool once = false;
+  if (!once) {
+    for (const auto& row : kern)
+      for (const Kern k : row) (void)set_lds_max(k);
+    once = true;
+  }
+  const bool cbig = (p.C % KW) == 0;
+  hipLaunchKernelGGL(kern[cbig][stats], dim3(grid), dim3(WM * WN * 64), lds, st, p);
   return true;
 }
 
@@ -827,11 +671,7 @@ static void wlaunch_p3p(const WgradParams& p, int splits, hipStream_t st) {
     (void)set_lds_max(conv_wgrad_p3_persist_kernel<WM, WN, TM, TN, false, OCC>);
     once = true;
   }
-  const int cus = p3p_cus();
-  const int items = tiles * splits;
-  const int per_cu = (int)((160 * 1024) / lds) < OCC ? (int)((160 * 1024) / lds) : OCC;
-  const int slots = cus * (per_cu > 0 ? per_cu : 1);
-  const int grid = items < slots ? items : slots;
+  const int grid = p3p_grid(tiles * splits, lds, OCC);
   const dim3 b(WM * WN * 64);
   if ((p.C % BN) == 0)
     hipLaunchKernelGGL((conv_wgrad_p3_persist_kernel<WM, WN, TM, TN, true, OCC>), dim3(grid), b, lds, st, p, splits);

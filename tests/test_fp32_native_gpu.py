@@ -213,6 +213,45 @@ def test_retired_p3_cfgs_run_their_fallback(fp32_mode, retired_case, cfg):
     assert rel_err(out[0][0], ref) < 3e-6
 
 
+@pytest.fixture(scope="module")
+def bnb_fallback_case():
+    """One BN-fused 1x1 data gradient with a row tail (2645 rows), a column tail (96 input channels
+    against 64 / 128-wide tiles) and a short K (64), shared by every persistent number."""
+    cin, cout, H, N = 96, 64, 23, 5
+    spec, p, pk, ps = _conv(cin, cout, 1, 1, 0)
+    torch.manual_seed(11)
+    dz = Fn.to_planes(torch.randn(N, H, H, cout, device=DEV))
+    z = torch.randn(N, H, H, cin, device=DEV) * 1.5 + 0.2
+    y = Fn.to_planes(torch.relu(torch.randn(N, H, H, cin, device=DEV)))
+    saved = Fn.BNSaved(torch.randn(cin, device=DEV) * 0.1, torch.rand(cin, device=DEV) + 0.5)
+    gamma, beta = torch.rand(cin, device=DEV) + 0.5, torch.randn(cin, device=DEV) * 0.1
+    base = torch.randn(N, H, H, cin, device=DEV)
+    return spec, p, pk, ps, dz, z, y, saved, gamma, beta, base
+
+
+@pytest.mark.parametrize("cfg", sorted(Fn._P3_PERSIST))
+def test_persistent_p3_cfgs_run_the_twin_for_fused_bn_backward(fp32_mode, bnb_fallback_case, cfg):
+    """The persistent plane GEMMs (cfg 18-22, 31-36) have no fused BN-backward epilogue (built, measured
+    slower and removed: profiles/retire_persistent_bnb.txt). A plan that names one for a BN-fused data
+    gradient runs the row's fallback chain down to the per-tile twin: dx and the accumulator bitwise
+    equal to the twin cfg's (deterministic mode: one add per accumulator slot)."""
+    spec, p, pk, ps, dz, z, y, saved, gamma, beta, base = bnb_fallback_case
+    cin = base.shape[-1]
+    R = Fn.det_replicas(base.numel() // cin)
+    out = []
+    Fn.set_deterministic(True)
+    try:
+        for c in (cfg, Fn._P3_PERSIST[cfg]):
+            acc = torch.zeros(R, 2, cin, device=DEV)
+            dx = base.clone()
+            Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, True, cfg=(c, 1),
+                          bnb=Fn.BNBwdFuse(z, y, saved, gamma, beta, 2, acc, R))
+            out.append((dx, acc))
+    finally:
+        Fn.set_deterministic(False)
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+
+
 @pytest.mark.parametrize("C", [64, 256, 2048])
 @pytest.mark.parametrize("relu,residual", [(True, False), (True, True), (False, False)])
 def test_fp32_bn_kernels_match_cpu(fp32_mode, C, relu, residual):
@@ -442,10 +481,11 @@ def test_fp32_fused_bn_backward_matches_unfused(fp32_mode, case, mode):
 @pytest.mark.parametrize("case", [(96, 64, 1, 23, 5, False), (64, 64, 3, 30, 3, True), (256, 128, 1, 14, 4, True)],
                          ids=lambda c: f"{c[0]}x{c[1]}k{c[2]}H{c[3]}N{c[4]}acc{int(c[5])}")
 def test_fp32_persistent_fused_bn_backward(fp32_mode, cfg, case):
-    """The persistent plane GEMM's BNB register epilogue (conv_p3_persist.h, a fused BN-backward data
-    gradient walking several tiles per workgroup): g for
-    modes 0 / 1 / 2 with and without the beta source, row tails (2645 rows) and a 96-column tail,
-    sum(g) / sum(g * xhat) against fp64, and the deterministic replicas bitwise reproducible."""
+    """A plan that names a persistent cfg (18-22) for a BN-fused data gradient: the persistent kernel
+    has no fused BN-backward epilogue (it was measured slower and removed), so the row's fallback runs,
+    down to the per-tile twin, and the result still meets fp64: g for modes 0 / 1 / 2 with and without
+    the beta source, row tails (2645 rows) and a 96-column tail, sum(g) / sum(g * xhat) against fp64,
+    and the deterministic replicas bitwise reproducible."""
     cin, cout, k, H, N, accumulate = case
     pad = k // 2
     spec, p, pk, ps = _conv(cin, cout, k, 1, pad)
@@ -464,31 +504,27 @@ def test_fp32_persistent_fused_bn_backward(fp32_mode, cfg, case):
     base = torch.randn(N, H, H, cin, device=DEV) if accumulate else None
     M = N * H * H
     xh = ((z.double() - mean.double()) * invstd.double()).cpu()
-    Fn.set_p3p_bnb(2)  # every mode on the persistent kernel (the default, 0, runs the twin)
-    try:
-        for mode in (0, 1, 2):
-            g = ref + (base.double().cpu() if accumulate else 0)
-            if mode == 1:
-                g = g * (yf.cpu() > 0).double()
-            elif mode == 2:
-                g = g * ((xh * gamma.double().cpu() + beta.double().cpu()) > 0).double()
-            R = 8
-            acc = torch.zeros(R, 2, cin, device=DEV)
-            dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
-            bnb = Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, mode, acc, R)
-            Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1), bnb=bnb)
-            assert rel_err(dx, g) < 3e-6, mode
-            a = acc.double().sum(0).cpu()
-            assert rel_err(a[0], g.reshape(-1, cin).sum(0)) < 1e-5, mode
-            assert rel_err(a[1], (g.reshape(-1, cin) * xh.reshape(-1, cin)).sum(0)) < 1e-5, mode
-        Rd = Fn.det_replicas(M)
-        runs = []
-        for _ in range(2):
-            a = torch.zeros(Rd, 2, cin, device=DEV)
-            dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
-            Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1),
-                          bnb=Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, 2, a, Rd))
-            runs.append((a, dx))
-        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
-    finally:
-        Fn.set_p3p_bnb(0)
+    for mode in (0, 1, 2):
+        g = ref + (base.double().cpu() if accumulate else 0)
+        if mode == 1:
+            g = g * (yf.cpu() > 0).double()
+        elif mode == 2:
+            g = g * ((xh * gamma.double().cpu() + beta.double().cpu()) > 0).double()
+        R = 8
+        acc = torch.zeros(R, 2, cin, device=DEV)
+        dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
+        bnb = Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, mode, acc, R)
+        Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1), bnb=bnb)
+        assert rel_err(dx, g) < 3e-6, mode
+        a = acc.double().sum(0).cpu()
+        assert rel_err(a[0], g.reshape(-1, cin).sum(0)) < 1e-5, mode
+        assert rel_err(a[1], (g.reshape(-1, cin) * xh.reshape(-1, cin)).sum(0)) < 1e-5, mode
+    Rd = Fn.det_replicas(M)
+    runs = []
+    for _ in range(2):
+        a = torch.zeros(Rd, 2, cin, device=DEV)
+        dx = base.clone() if accumulate else torch.zeros(N, H, H, cin, device=DEV)
+        Fn.conv_dgrad(dz, spec, pk.tr, p.data, dx, accumulate, cfg=(cfg, 1),
+                      bnb=Fn.BNBwdFuse(z, y, Fn.BNSaved(mean, invstd), gamma, beta, 2, a, Rd))
+        runs.append((a, dx))
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])

@@ -30,6 +30,6 @@ def test_kernel_ops_registered_in_both_builds():
             pytest.skip(f"{name} not built")
         torch.ops.load_library(path)
         lib = getattr(torch.ops, ns)
-        for op in ("conv_p3", "conv_p3_bnb", "conv_wgrad_p3", "conv_igemm", "bn_stats_acc", "set_p3p_bnb",
-                   "set_deterministic", "bn_bwd_apply_acc"):
+        for op in ("conv_p3", "conv_p3_bnb", "conv_wgrad_p3", "conv_igemm", "bn_stats_acc", "set_deterministic",
+                   "bn_bwd_apply_acc"):
             assert hasattr(lib, op), (ns, op)

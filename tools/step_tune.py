@@ -158,8 +158,6 @@ def main():
     ap.add_argument("--try_plan", action="append", default=[],
                     help="interleaved in-step A/B of one plan change instead of tuning: kind,M,N,K,taps=cfg,splits "
                          "(repeatable; each tried alone against the current table)")
-    ap.add_argument("--knob_ab", default="",
-                    help="interleaved in-step A/B of a kernel switch instead of tuning: p3p_bnb:A:B")
     ap.add_argument("--out", default="gpurun_out/step_tune.json")
     a = ap.parse_args()
     t_start = time.time()
@@ -182,7 +180,7 @@ def main():
 
     # isolated timing of every candidate (ranking and candidate shortlist)
     iso = {}
-    for k, (cnt, cands, run) in ([] if a.aa_only or a.knob_ab or a.try_plan else probs.items()):
+    for k, (cnt, cands, run) in ([] if a.aa_only or a.try_plan else probs.items()):
         iso[k] = {json.dumps(c): autotune._time(lambda: run(c)) for c in cands}
         cur = json.dumps(Fn._tuned[k] if not isinstance(Fn._tuned[k], tuple) else list(Fn._tuned[k]))
         if cur not in iso[k]:
@@ -197,7 +195,7 @@ def main():
         return json.dumps(list(v) if isinstance(v, tuple) else v)
 
     kinds = [k for k in a.kinds.split(",") if k]
-    order = [] if a.aa_only or a.knob_ab or a.try_plan else sorted((k for k in probs if not kinds or k[0] in kinds),
+    order = [] if a.aa_only or a.try_plan else sorted((k for k in probs if not kinds or k[0] in kinds),
                                         key=lambda k: -iso[k][cur_s(k)] * probs[k][0])
 
     images, labels = synthetic_batch(model, a.batch)
@@ -222,18 +220,6 @@ def main():
             ta, tb = ab(timer, key, cur, cand, a.aa_reps * a.rounds)
             log(f"[step_tune] try {key}: {cur} {ta:.4f} ms/step vs {cand} {tb:.4f} ms/step ({100 * (ta - tb) / ta:+.2f}%; "
                 f"A/A band {100 * noise / t0:.2f}%)")
-        return
-    if a.knob_ab:
-        name, va, vb = a.knob_ab.split(":")
-        setter = {"p3p_bnb": Fn.set_p3p_bnb}[name]
-        ta, tb = [], []
-        for r in range(a.aa_reps * a.rounds):  # ABBA
-            for v, t in (((va, ta), (vb, tb)) if r % 2 == 0 else ((vb, tb), (va, ta))):
-                setter(int(v))
-                t.append(timer.measure())
-        ma, mb = statistics.median(ta), statistics.median(tb)
-        log(f"[step_tune] knob {name}: {va} {ma:.4f} ms/step vs {vb} {mb:.4f} ms/step ({100 * (ma - mb) / ma:+.2f}%; "
-            f"A/A band {100 * noise / t0:.2f}%) A: {' '.join(f'{x:.4f}' for x in ta)} B: {' '.join(f'{x:.4f}' for x in tb)}")
         return
     if a.aa_only:
         return
