@@ -178,7 +178,13 @@ def planes_mode() -> bool:
 
 def to_planes(x: torch.Tensor) -> Planes:
     """fp32 [..., C] (C % 8 == 0; rows may be strided) -> Planes of the same logical shape (one
-    launch on the GPU)."""
+    launch on the GPU).
+
+    ``from_planes(to_planes(x))`` returns x bit for bit for finite x with 2^-100 <= |x| <= 2^127
+    and for +0. Outside that domain: -0.0 comes back as +0.0 (equal, other bits); below
+    2^-110 the lo plane underflows bf16 and the value is only approximate (within 2^-134);
+    where the hi plane rounds to Inf (|x| within half a bf16 step of 2^128, e.g. 3.4e38) the residual is Inf - Inf
+    and the merged value is NaN; Inf and NaN inputs merge to NaN."""
     if isinstance(x, Planes):
         return x
     assert x.dtype == torch.float32 and x.shape[-1] % 8 == 0
@@ -1633,14 +1639,15 @@ def nonfinite(g, flag):
 
 
 def loss_total(row_loss, B: int, l2, half_wd: float, loss):
-    """loss[0] = mean(row_loss[:B]) + half_wd * l2[0] (l2 None: the mean alone) -- the step's reported
-    loss in one launch (tf_cnn_benchmarks' total_loss = cross entropy + weight decay * l2 term)."""
+    """loss[0] = mean(row_loss[:B]) + half_wd * sum(l2) (l2 None: the mean alone; l2 is one slot, or
+    the optimizer's per-block partials) -- the step's reported loss in one launch (tf_cnn_benchmarks'
+    total_loss = cross entropy + weight decay * l2 term)."""
     if row_loss.is_cuda:
         _ext.ops().loss_total(row_loss, B, l2, half_wd, loss)
         return
     t = row_loss[:B].mean()
     if l2 is not None:
-        t = t + half_wd * l2.view(-1)[0]
+        t = t + half_wd * l2.sum()
     loss.view(-1)[0] = t
 
 

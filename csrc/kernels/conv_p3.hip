@@ -79,7 +79,9 @@ void launch_wgrad_p3(const WgradParams& p, int cfg, int splits, hipStream_t st) 
 // ============================================================== plane split / merge
 // x fp32 [rows][ldx] (C channels used) -> three bf16 planes [3][rows][ldo] (plane stride `plane`
 // elements): hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (round to nearest even;
-// hi + mid + lo == x for every normal fp32 value)
+// hi + mid + lo == x for finite 2^-100 <= |x| <= 2^127 and for +0; -0 merges to +0, below
+// 2^-110 the lo plane underflows bf16 (the merged value is within 2^-134), and where hi rounds to Inf the merged value is NaN:
+// tests/test_loss_ref_cpu.py pins the domain)
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int ldx, int C, int64_t n8,
                                                            uint16_t* __restrict__ out, int ldo, int64_t plane) {
   const int CV = C >> 3;
