@@ -30,6 +30,26 @@ def _resnet_cifar(depth):
 
 # the CIFAR-10 ResNets (32 x 32 input): built only with --data_name=cifar10
 CIFAR_MODELS = ("resnet20", "resnet32", "resnet44", "resnet56", "resnet110")
+# the CIFAR-10 DenseNets (growth rate 12), under the same rule: a tuple of their own beside the ResNets'
+CIFAR_DENSENETS = ("densenet40_k12", "densenet100_k12")
+# upstream names this project refuses, with the reason
+REFUSED_MODELS = {
+    "densenet100_k24": "its third dense block reaches 2,320 channels and the BatchNorm kernels stop at C <= 2048",
+}
+
+
+def cifar_only_models():
+    """Every model that exists for --data_name=cifar10 only."""
+    return CIFAR_MODELS + CIFAR_DENSENETS
+
+
+def _densenet_cifar(depth):
+    def make(**kw):
+        from .densenet_cifar import DenseNetCifar
+
+        return DenseNetCifar(depth=depth, growth=12, **kw)
+
+    return make
 
 
 def _inception3(**kw):
@@ -70,6 +90,8 @@ _MODELS = {
     "resnet101_v2": _resnet_v2(101),
     "resnet152_v2": _resnet_v2(152),
     **{name: _resnet_cifar(int(name[len("resnet"):])) for name in CIFAR_MODELS},
+    "densenet40_k12": _densenet_cifar(40),
+    "densenet100_k12": _densenet_cifar(100),
     "inception3": _inception3,
     "mobilenet": _mobilenet,
     "trivial": _trivial,
@@ -104,9 +126,11 @@ def create_model(name: str, data_name: str = None, **kw) -> CNNModel:
     override = _DATASET_MODELS.get(data_name or "imagenet", {})
     if name in override:
         return override[name](**kw)
+    if name in REFUSED_MODELS:
+        raise ValueError(f"--model={name} is refused: {REFUSED_MODELS[name]}")
     if name not in _MODELS:
         raise ValueError(f"unknown model {name!r}; available: {', '.join(model_names())}")
     return _MODELS[name](**kw)
 
 
-__all__ = ["create_model", "model_names", "dataset_model_names", "CNNModel", "ResNet"]
+__all__ = ["create_model", "model_names", "dataset_model_names", "cifar_only_models", "CNNModel", "ResNet"]

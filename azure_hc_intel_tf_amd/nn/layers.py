@@ -1016,3 +1016,228 @@ class Logits(Layer):
 
     def params(self):
         return [self.w, self.b]
+
+
+# ------------------------------------------------------------------------------ DenseNet
+# DenseNet dense layers (BN -> ReLU -> conv 3x3 with k outputs) in one launch each (csrc/kernels/
+# dense3x3.hip, Fn.dense_conv3x3_forward). False: bn_apply_acc writes the normalised operand and the
+# existing conv GEMM (16 output columns) writes the slot, on the same layout -- the A/B partner
+FUSE_DENSE = _env_on("HCB_FUSE_DENSE")
+
+
+def dense_channel_mask(c0: int, n: int, k: int) -> torch.Tensor:
+    """True for the real channels of a dense block's buffer after n layers, False for the structural pads.
+
+    Layout: the block owns ONE NHWC buffer of c0 + 16 n channels. Channels [0, c0) hold the block input (c0
+    a multiple of 8); layer i reads channels [0, c0 + 16 i) and writes slot i = [c0 + 16 i, c0 + 16 i + 16) in
+    place through the row stride -- no concat copy, forward or backward. The last 16 - k channels of a slot
+    are pads. Why they stay zero without any masking in the step: a pad channel is 0 at every pixel (the
+    producing kernel stores literal zeros), so its batch mean and variance are 0 and xhat = 0; its beta
+    starts at 0 (gamma at 0 too), so every BN that reads it outputs 0, and ReLU's mask (y > 0) is closed.
+    Hence, for the pad channel: dgamma = sum(g * xhat) = 0 and dbeta = sum(g) = 0 with g = dy * mask = 0, so
+    gamma and beta never move; the BN's dx is scale * (g - mean(g) - xhat * mean(g * xhat)) = 0; every conv
+    weight that multiplies it has dW = sum(dz * 0) = 0 and starts at 0, and weight decay and momentum keep
+    a zero at zero; a slot's pad OUTPUT rows of the kernel have dz = 0 (nothing but zero weights reads
+    them), so their dW is 0 as well. Parameter storage behind pads is bit-zero and stays so; parameter
+    counts (logical_numel) and the L2 term are those of the real channels."""
+    m = torch.ones(c0 + Fn.DENSE_SLOT * n, dtype=torch.bool)
+    for i in range(n):
+        m[c0 + Fn.DENSE_SLOT * i + k:c0 + Fn.DENSE_SLOT * (i + 1)] = False
+    return m
+
+
+def mask_param(p, keep: torch.Tensor, dim: int) -> None:
+    """Zero ``p``'s initial value where ``keep`` (along ``dim``) is False and count only the kept part."""
+    init, shape = p.init, [1] * len(p.shape)
+    shape[dim] = -1
+
+    def f(t):
+        init(t)
+        t.mul_(keep.view(shape).to(t.dtype))
+
+    p.init = f
+    p.logical_numel = p.logical_numel // p.shape[dim] * int(keep.sum())
+
+
+class _DenseLayer:
+    def __init__(self, ps: ParamStore, name: str, c_in: int, k: int, keep: torch.Tensor, eps: float):
+        S = Fn.DENSE_SLOT
+        self.c_in, self.slot = c_in, c_in
+        self.spec = ConvSpec(cin=c_in, cin_pad=c_in, cout=S, kh=3, kw=3, pt=1, pl=1, pb=1, pr=1)
+        self.w = ps.add(f"{name}/conv2d/kernel", (S, 3, 3, c_in), True, ps.trunc_normal(math.sqrt(2.0 / 9 / k)),
+                        logical_numel=k * 9 * c_in)
+        mask_param(self.w, keep, 3)
+        mask_param(self.w, torch.arange(S) < k, 0)
+        self.w.logical_numel = k * 9 * int(keep.sum())
+        self.pack = ps.add_pack(self.w, S, 3, 3, c_in, self.spec.Kpad, self.spec.Kpad_t, want_tr=True)
+        self.gamma = ps.add(f"{name}/batchnorm/gamma", (c_in,), False, ParamStore.const(1.0))
+        self.beta = ps.add(f"{name}/batchnorm/beta", (c_in,), False, ParamStore.const(0.0))
+        mask_param(self.gamma, keep, 0)
+        mask_param(self.beta, keep, 0)
+        self.rmean = ps.add_buffer(f"{name}/batchnorm/moving_mean", (c_in,), 0.0)
+        self.rvar = ps.add_buffer(f"{name}/batchnorm/moving_variance", (c_in,), 1.0)
+        self.acc_b = ps.add_stat(f"{name}/bn_acc_bwd", (STAT_R, 2, c_in))
+        self.acc_s = ps.add_stat(f"{name}/slot_acc", (STAT_R, 2, S))  # the unfused conv's slot statistics
+        self.sv_mean = ps.add_stat(f"{name}/bn_mean", (c_in,))
+        self.sv_invstd = ps.add_stat(f"{name}/bn_invstd", (c_in,))
+
+    def params(self):
+        return [self.w, self.beta, self.gamma]
+
+
+class DenseBlock(Layer):
+    """A DenseNet block of ``n`` layers BN -> ReLU -> conv 3x3 (k outputs) -> concat on the padded
+    in-place layout of ``dense_channel_mask``. The producer of the block input writes straight into
+    ``input_view`` (no copy); ``forward`` returns the whole buffer [N, H, W, c0 + 16 n]. The buffer's batch
+    statistics live in one accumulator (R replicas of [2][c_total]): the input's columns from bn_stats_acc,
+    each slot's from the kernel that produced it, read by every later layer -- nothing is reduced twice.
+    Backward (existing kernels on the padded layout): per layer, last to first, the normalised operand is
+    re-materialised by bn_apply_acc into a scratch shared by the block, the weight- and data-gradient GEMMs
+    run with 16 output columns on the layer's slot of the gradient buffer, and the BN backward adds into
+    the first c_in channels of that same gradient buffer (bn_bwd_apply_acc's ``add``)."""
+
+    def __init__(self, ps: ParamStore, name: str, in_shape, n: int, k: int = 12, eps: float = 1e-5,
+                 decay: float = 0.9):
+        H, W, c0 = in_shape
+        S = Fn.DENSE_SLOT
+        assert c0 % 8 == 0 and 1 <= k <= S, "dense block: C0 % 8, growth rate <= 16"
+        self.name, self.in_shape, self.c0, self.n, self.k = name, in_shape, c0, n, k
+        self.ctot = c0 + S * n
+        self.out_shape = (H, W, self.ctot)
+        self.eps, self.decay = eps, decay
+        self.keep = dense_channel_mask(c0, n, k)
+        self.subs = [_DenseLayer(ps, f"{name}/layer{i + 1}", c0 + S * i, k, self.keep[:c0 + S * i], eps)
+                     for i in range(n)]
+        self.acc = ps.add_stat(f"{name}/bn_acc", (STAT_R, 2, self.ctot))
+        self.acc0 = ps.add_stat(f"{name}/bn_acc_in", (STAT_R, 2, c0))
+        self.shift = ps.add_persist(f"{name}/bn_shift", (self.ctot,)) if BN_SHIFT else None
+        self.training = True
+        self._buf = self._st = self._ref = None
+
+    def params(self):
+        return [p for L in self.subs for p in L.params()]
+
+    def flops(self, batch: int) -> int:
+        H, W, _ = self.in_shape
+        return sum(2 * batch * H * W * self.k * 9 * int(self.keep[:L.c_in].sum()) for L in self.subs)
+
+    def input_view(self, N: int, dev):
+        H, W, _ = self.in_shape
+        self._buf = empty_act((N, H, W, self.ctot), dev)
+        return self._buf[..., :self.c0]
+
+    def _sh(self, a: int, b: int):
+        return self.shift.data[a:b] if self.shift is not None else None
+
+    # ------------------------------------------------------------------ forward
+    def forward(self):
+        buf = self._buf
+        if not Fn.native(buf):
+            return self._forward_ref(buf)
+        N, H, W, _ = buf.shape
+        S = Fn.DENSE_SLOT
+        if not self.training:
+            for L in self.subs:
+                if FUSE_DENSE:
+                    Fn.dense_conv3x3_forward(buf, L.c_in, L.slot, L.w.data[:self.k], L.gamma.data, L.beta.data, self.eps,
+                                             running_mean=L.rmean.data, running_var=L.rvar.data, wpack=L.pack.pack)
+                else:
+                    op = empty_op((N, H, W, L.c_in), buf.device)
+                    Fn.bn_inference(buf[..., :L.c_in], L.gamma.data, L.beta.data, L.rmean.data, L.rvar.data, self.eps,
+                                    op, True)
+                    Fn.conv_forward(op, L.spec, L.pack.pack, L.w.data, buf[..., L.slot:L.slot + S])
+            return buf
+        det = Fn.deterministic()
+        R = Fn.det_replicas(N * H * W) if det else STAT_R
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=buf.device)  # noqa: E731
+        acc, acc0 = (z(R, 2, self.ctot), z(R, 2, self.c0)) if det else (self.acc.data, self.acc0.data)
+        Fn.bn_stats_acc(buf[..., :self.c0], acc0, R, self._sh(0, self.c0))
+        acc[:, :, :self.c0].copy_(acc0)
+        for L in self.subs:
+            if FUSE_DENSE:
+                Fn.dense_conv3x3_forward(buf, L.c_in, L.slot, L.w.data[:self.k], L.gamma.data, L.beta.data, self.eps,
+                                         acc=acc, R=R, shift=self._sh(0, L.c_in), momentum=self.decay,
+                                         running_mean=L.rmean.data, running_var=L.rvar.data, saved_mean=L.sv_mean.data,
+                                         saved_invstd=L.sv_invstd.data, stats=acc, stats_R=R,
+                                         stats_shift=self._sh(L.slot, L.slot + S), wpack=L.pack.pack)
+            else:
+                op = empty_op((N, H, W, L.c_in), buf.device)
+                Fn.bn_forward_acc(buf[..., :L.c_in], L.gamma.data, L.beta.data, L.rmean.data, L.rvar.data, self.decay,
+                                  self.eps, op, True, acc[:, :, :L.c_in].contiguous(), R, L.sv_mean.data,
+                                  L.sv_invstd.data, shift=self._sh(0, L.c_in))
+                acc_s = z(R, 2, S) if det else L.acc_s.data
+                Fn.conv_forward(op, L.spec, L.pack.pack, L.w.data, buf[..., L.slot:L.slot + S], stats=acc_s, stats_R=R,
+                                stats_shift=self._sh(L.slot, L.slot + S))
+                acc[:, :, L.slot:L.slot + S].copy_(acc_s)
+        self._st = (acc, R)
+        return buf
+
+    # ------------------------------------------------------------------ backward
+    def backward(self, G):
+        """``G``: the gradient of the whole buffer [N, H, W, c_total] (plain, contiguous), accumulated into
+        in place; returns its first c0 channels, the gradient of the block input."""
+        if self._ref is not None:
+            return self._backward_ref(G)
+        buf, (acc, R) = self._buf, self._st
+        N, H, W, _ = buf.shape
+        S, dev = Fn.DENSE_SLOT, buf.device
+        cmax = self.subs[-1].c_in
+        op_all, da_all = empty_op((N, H, W, cmax), dev), empty_act((N, H, W, cmax), dev)
+        for L in reversed(self.subs):
+            c = L.c_in
+            x, op, da, Gin = buf[..., :c], op_all[..., :c], da_all[..., :c], G[..., :c]
+            Fn.bn_forward_acc(x, L.gamma.data, L.beta.data, None, None, 1.0, self.eps, op, True,
+                              acc[:, :, :c].contiguous(), R, L.sv_mean.data, L.sv_invstd.data, shift=self._sh(0, c))
+            dz = G[..., L.slot:L.slot + S]
+            if Fn.planes_mode():
+                dz = Fn.to_planes(dz)  # one split for both GEMMs
+            Fn.conv_wgrad(dz, op, L.spec, L.w.grad.view(S, -1))
+            Fn.conv_dgrad(dz, L.spec, L.pack.tr, L.w.data, da, False)
+            acc_b = (torch.zeros((R, 2, c), dtype=torch.float32, device=dev) if Fn.deterministic() else L.acc_b.data)
+            Fn.bn_backward_acc(da, None, x, Fn.BNSaved(L.sv_mean.data, L.sv_invstd.data), L.gamma.data, L.beta.data, 2,
+                               L.gamma.grad, L.beta.grad, Gin, acc_b, R, add=Gin)
+        if self.shift is not None:  # the next step's shift: this step's batch means (every reader is done)
+            last = self.subs[-1]
+            self.shift.data[:last.c_in].copy_(last.sv_mean.data)
+        self._buf = self._st = None
+        return G[..., :self.c0]
+
+    # ------------------------------------------------------------------ PyTorch path (CPU, non-native dtypes)
+    def _forward_ref(self, buf):
+        S, M = Fn.DENSE_SLOT, buf.numel() // buf.shape[-1]
+        if not self.training:
+            for L in self.subs:
+                Fn.dense_conv3x3_forward(buf, L.c_in, L.slot, L.w.data[:self.k], L.gamma.data, L.beta.data, self.eps,
+                                         running_mean=L.rmean.data, running_var=L.rvar.data)
+            return buf
+        dt = buf.dtype
+        with torch.enable_grad():
+            x0 = buf[..., :self.c0].detach().clone().requires_grad_(True)
+            leaves, cur = [], x0
+            for L in self.subs:
+                w, g, b = (t.data.detach().to(dt).requires_grad_(True) for t in (L.w, L.gamma, L.beta))
+                leaves.append((w, g, b))
+                mean, var = cur.mean((0, 1, 2)), cur.var((0, 1, 2), unbiased=False)
+                with torch.no_grad():
+                    L.rmean.data.mul_(self.decay).add_((1 - self.decay) * mean.detach().float())
+                    L.rvar.data.mul_(self.decay).add_((1 - self.decay) * var.detach().float() * M / max(M - 1, 1))
+                a = torch.relu((cur - mean) * torch.rsqrt(var + self.eps) * g + b)
+                y = torch.nn.functional.conv2d(a.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1)
+                cur = torch.cat([cur, y], 3)
+        buf.copy_(cur.detach())
+        self._ref = (x0, leaves, cur)
+        return buf
+
+    def _backward_ref(self, G):
+        x0, leaves, out = self._ref
+        flat = [x0] + [t for trip in leaves for t in trip]
+        grads = torch.autograd.grad(out, flat, G.to(out.dtype))
+        for L, i in zip(self.subs, range(1, len(flat), 3)):
+            L.w.grad.add_(grads[i].float())
+            L.gamma.grad.add_(grads[i + 1].float())
+            L.beta.grad.add_(grads[i + 2].float())
+        self._ref = self._buf = None
+        return grads[0]
+
+    def clear(self):
+        self._buf = self._st = self._ref = None

@@ -1532,6 +1532,99 @@ def lrn_backward(dy, x, dx, r: int, bias: float, alpha: float, beta: float):
     return dx
 
 
+# ------------------------------------------------- DenseNet dense layer (BN-ReLU-conv3x3)
+DENSE_SLOT = 16  # channels a dense layer writes: its growth rate (<= 16) padded with structural zeros
+
+
+def dense_pack(w, dtype):
+    """The GEMM operands of a dense layer's fp32 kernel ``w`` [nout, 3, 3, C] outside a ParamStore (tools,
+    tests; a model's packs come from ParamStore.repack): the flat ``[nout * Kpad]`` pack in ``dtype`` --
+    K = (tap, c), Kpad = K rounded up to 64 -- and, for the fp32 path (``dtype`` float32: a bf16 pack), the
+    [2][n] mid / lo packs of the three-way split, else None."""
+    nout, C = w.shape[0], w.shape[3]
+    K = 9 * C
+    full = torch.zeros((nout, _round_up(K, 64)), dtype=torch.float32, device=w.device)
+    full[:, :K] = w.reshape(nout, K)
+    if dtype != torch.float32:
+        return full.to(dtype).reshape(-1), None
+    hi = full.to(torch.bfloat16)
+    r = full - hi.float()
+    mid = r.to(torch.bfloat16)
+    lo = (r - mid.float()).to(torch.bfloat16)
+    return hi.reshape(-1), torch.stack([mid.reshape(-1), lo.reshape(-1)])
+
+
+def dense_conv3x3_forward(buf, c_in: int, slot: int, w, gamma, beta, eps: float, acc=None, R: int = 1, shift=None,
+                          momentum: float = 1.0, running_mean=None, running_var=None, saved_mean=None,
+                          saved_invstd=None, stats=None, stats_R: int = 0, stats_shift=None, wpack=None, wpack_lo=None):
+    """One DenseNet layer on its block's NHWC concat buffer ``buf`` [N, H, W, ld], in place:
+
+        buf[..., slot : slot + nout] = conv3x3_SAME_s1(relu(gamma * (x - mean) * invstd + beta)),  x = buf[..., :c_in]
+
+    and ``buf[..., slot + nout : slot + 16] = 0`` (the slot's structural pad; ``slot >= c_in``, both multiples
+    of 8). ``w``: the fp32 kernel [nout, 3, 3, c_in], nout <= 16, no bias. Training (``acc`` given): mean /
+    invstd are the batch moments of x, finalised from ``acc`` -- R replicas of [2][>= c_in] holding
+    sum(x - shift), sum((x - shift)^2) per buffer channel, accumulated when each slot was produced -- and
+    written to ``saved_mean`` / ``saved_invstd``; the moving statistics are updated with ``momentum`` (the
+    decay) when given. Inference (``acc`` None): mean / variance are ``running_mean`` / ``running_var``.
+    ``stats`` ([>= stats_R][2][>= slot + 16], usually ``acc`` itself): receives the new slot's sums
+    sum(y - stats_shift), sum((y - stats_shift)^2) at columns slot .. slot + 16, for the layers that follow.
+
+    GPU (csrc/kernels/dense3x3.hip): ONE launch; the normalised operand is never written. 16-bit buffers
+    take the 16-bit pack ``wpack``; an fp32 buffer (a plain tensor, not Planes) is normalised in fp32, split
+    into bf16 hi / mid / lo on its way into LDS and multiplied bf16x6 with the plane pack (``wpack`` hi,
+    ``wpack_lo`` or the pack's registered mid / lo). Without ``wpack`` the operands are packed from ``w`` here
+    (dense_pack: tools and tests). CPU / non-native tensors: the formula above in PyTorch at ``buf``'s dtype,
+    which is the definition."""
+    N, H, W, _ = buf.shape
+    nout = w.shape[0]
+    M = N * H * W
+    assert nout <= DENSE_SLOT and tuple(w.shape[1:]) == (3, 3, c_in), "dense_conv3x3_forward: w is [nout <= 16, 3, 3, c_in]"
+    assert slot >= c_in and slot + DENSE_SLOT <= buf.shape[3], "dense_conv3x3_forward: the slot lies beyond c_in, inside buf"
+    assert acc is not None or (running_mean is not None and running_var is not None), "inference needs moving statistics"
+    if native(buf):
+        assert not is_planes(buf), "the dense-layer kernel reads and writes plain tensors"
+        if wpack is None:
+            wpack, wpack_lo = dense_pack(w, buf.dtype)
+        elif wpack_lo is None:
+            wpack_lo = lo_pack(wpack)
+        if acc is None:
+            # moving statistics as one replica of shifted sums (bn_inference's form): shift = the moving
+            # mean, sum 0, sum of squares M * moving variance; nothing is updated
+            acc = torch.stack([torch.zeros_like(running_var), running_var * float(M)]).unsqueeze(0).contiguous()
+            R, shift, running_mean, running_var, momentum = 1, running_mean, None, None, 1.0
+        kpad = _round_up(9 * c_in, 64)  # the pack rows' stride (ConvSpec.Kpad); a 16-row pack's pad rows are not read
+        _ext.ops().dense_conv3x3_fwd(buf, wpack, wpack_lo, buf, [N, H, W, c_in, ld(buf), slot, ld(buf), nout, kpad],
+                                     acc, int(R), float(eps), float(momentum), gamma, beta, shift, saved_mean,
+                                     saved_invstd, running_mean, running_var, stats, int(stats_R), int(slot), stats_shift)
+        return buf
+    dt = buf.dtype
+    x = buf[..., :c_in]
+    if acc is not None:
+        sums = acc[:R].sum(0)[:, :c_in]
+        d = sums[0] / M
+        mean = d + (shift[:c_in] if shift is not None else 0)
+        var = (sums[1] / M - d * d).clamp(min=0)
+        invstd = torch.rsqrt(var + eps)
+        if saved_mean is not None:
+            saved_mean[:c_in] = mean
+            saved_invstd[:c_in] = invstd
+        if running_mean is not None:
+            running_mean[:c_in].mul_(momentum).add_((1 - momentum) * mean)
+            running_var[:c_in].mul_(momentum).add_((1 - momentum) * var * M / max(M - 1, 1))
+    else:
+        mean, invstd = running_mean[:c_in], torch.rsqrt(running_var[:c_in] + eps)
+    a = torch.relu((x - mean.to(dt)) * (invstd * gamma[:c_in]).to(dt) + beta[:c_in].to(dt))
+    y = F.conv2d(a.permute(0, 3, 1, 2), w.to(dt).permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1)
+    buf[..., slot:slot + nout] = y
+    buf[..., slot + nout:slot + DENSE_SLOT] = 0
+    if stats is not None:
+        dy = y.reshape(M, nout).to(stats.dtype) - (stats_shift[:nout] if stats_shift is not None else 0)
+        stats[0, 0, slot:slot + nout] += dy.sum(0)
+        stats[0, 1, slot:slot + nout] += (dy * dy).sum(0)
+    return buf
+
+
 # ------------------------------------------------------------------------- loss
 def softmax_xent(logits, labels, ncls, row_loss, dlogits, scale, scale_dev=None, dl32=None,
                  label_smoothing: float = 0.0):

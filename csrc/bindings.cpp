@@ -1497,6 +1497,103 @@ void lrn_bwd(const Tensor& dy, const Tensor& x, const Tensor& dx, int64_t r, dou
   hcb::launch_lrn_bwd(p, xf, cur_stream());
 }
 
+// ---- DenseNet dense layer (dense3x3.hip): y[:, slot : slot + 16] = conv3x3(relu(BN(x[:, 0:C]))) in one
+// pass. geom = [N, H, W, C, ldx, slot, ldy, Nout, Kpad]: x / y the raw NHWC buffers (they may be one
+// buffer: the slot then lies at or beyond channel C), 16-bit or fp32 alike; w the [Nout][Kpad] pack
+// (16-bit; fp32: the bf16 hi pack with w_lo = [2][n] mid / lo packs); acc the R replicas of [2][acc_C]
+// holding x's batch statistics (column = buffer channel); stats: the replicas that receive the slot's
+// statistics at columns stats_off .. + 16 (usually acc itself, stats_off = slot)
+void dense_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& w_lo, const Tensor& y,
+                       at::IntArrayRef g, const Tensor& acc, int64_t R, double eps, double momentum,
+                       const Tensor& gamma, const Tensor& beta, const c10::optional<Tensor>& shift,
+                       const c10::optional<Tensor>& saved_mean, const c10::optional<Tensor>& saved_invstd,
+                       const c10::optional<Tensor>& run_mean, const c10::optional<Tensor>& run_var,
+                       const c10::optional<Tensor>& stats, int64_t stats_R, int64_t stats_off,
+                       const c10::optional<Tensor>& stats_shift) {
+  TORCH_CHECK(g.size() == 9, "hcb.dense_conv3x3_fwd: geom = [N, H, W, C, ldx, slot, ldy, Nout, Kpad]");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], slot = g[5], ldy = g[6], Nout = g[7], Kpad = g[8];
+  const bool f32 = check_act_or_f32(x, "x");
+  same_act(x, y, "y");
+  check_act(w, "w");
+  const int64_t e = f32 ? 4 : 2;
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.dense_conv3x3_fwd: empty tensor");
+  TORCH_CHECK(C >= 8 && C % 8 == 0, "hcb.dense_conv3x3_fwd: C_in must be a multiple of 8, got ", C);
+  TORCH_CHECK(C <= 2048, "hcb.dense_conv3x3_fwd: C_in <= 2048 (the BatchNorm kernels' limit), got ", C);
+  TORCH_CHECK(slot >= 0 && slot % 8 == 0, "hcb.dense_conv3x3_fwd: the slot offset must be a multiple of 8, got ", slot);
+  TORCH_CHECK(ldx % 8 == 0 && ldy % 8 == 0, "hcb.dense_conv3x3_fwd: ld must be a multiple of 8, got ", ldx, " / ", ldy);
+  TORCH_CHECK(ldx >= C && ldy >= slot + 16, "hcb.dense_conv3x3_fwd: rows of ", ldx, " / ", ldy,
+              " channels do not hold C_in = ", C, " / the slot at ", slot);
+  TORCH_CHECK(Nout >= 1 && Nout <= 16, "hcb.dense_conv3x3_fwd: Nout <= 16 (one MFMA tile of output channels), got ", Nout);
+  TORCH_CHECK(x.stride(-1) == 1 && y.stride(-1) == 1, "hcb.dense_conv3x3_fwd: non-contiguous rows (channel stride must be 1)");
+  TORCH_CHECK(Kpad % 8 == 0 && Kpad >= 9 * C, "hcb.dense_conv3x3_fwd: Kpad must be a multiple of 8 >= 9 * C_in");
+  TORCH_CHECK(hcb::dense_conv3x3_fits((int)N, (int)H, (int)W, (int)C, f32),
+              "hcb.dense_conv3x3_fwd: W = ", W, " with C_in = ", C, " is larger than the input patch the LDS budget allows");
+  const int64_t M = N * H * W;
+  const int64_t xb = ((M - 1) * ldx + C) * e, yb = ((M - 1) * ldy + slot + 16) * e, wb = Nout * Kpad * 2;
+  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31) && wb < (1ll << 31),
+              "hcb.dense_conv3x3_fwd: tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(y, yb, "y");
+  check_range(w, wb, "w");
+  check_align16(x.data_ptr(), "x");
+  check_align16(y.data_ptr(), "y");
+  check_align16(w.data_ptr(), "w");
+  // one buffer (or overlapping ones): the slot must not be one of the channels other workgroups still read
+  const char *xp = (const char*)x.data_ptr(), *yp = (const char*)y.data_ptr();
+  if (xp < yp + yb && yp < xp + xb)
+    TORCH_CHECK(xp == yp && ldx == ldy && slot >= C, "hcb.dense_conv3x3_fwd: x and y overlap: one buffer, slot >= C_in");
+  hcb::DenseParams p{};
+  p.x = x.data_ptr();
+  p.y = (char*)y.data_ptr() + slot * e;
+  p.w = w.data_ptr();
+  if (f32) {
+    TORCH_CHECK(w_lo.has_value() && w_lo->dim() == 2 && w_lo->size(0) == 2 && w_lo->stride(1) == 1 &&
+                    w_lo->scalar_type() == w.scalar_type() && w_lo->size(1) >= Nout * Kpad,
+                "hcb.dense_conv3x3_fwd: fp32 needs w_lo = [2][>= Nout*Kpad] of the pack's type");
+    check_cuda(*w_lo, "w_lo");
+    const Tensor m = w_lo->select(0, 0), l = w_lo->select(0, 1);
+    check_align16(m.data_ptr(), "w_lo[0]");
+    check_align16(l.data_ptr(), "w_lo[1]");
+    p.w_mid = m.data_ptr();
+    p.w_lo = l.data_ptr();
+  }
+  check_f32(acc, "acc");
+  TORCH_CHECK(R >= 1 && acc.dim() == 3 && acc.is_contiguous() && acc.size(0) >= R && acc.size(1) == 2 && acc.size(2) >= C,
+              "hcb.dense_conv3x3_fwd: acc must be contiguous [>= R][2][>= C_in]");
+  p.acc = acc.data_ptr<float>();
+  p.R = (int)R;
+  p.acc_C = (int)acc.size(2);
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.shift = opt_f32(shift, C, "shift");
+  p.eps = (float)eps;
+  p.momentum = (float)momentum;
+  p.saved_mean = const_cast<float*>(opt_f32(saved_mean, C, "saved_mean"));
+  p.saved_invstd = const_cast<float*>(opt_f32(saved_invstd, C, "saved_invstd"));
+  TORCH_CHECK(run_mean.has_value() == run_var.has_value(), "hcb.dense_conv3x3_fwd: moving mean and variance come together");
+  p.run_mean = const_cast<float*>(opt_f32(run_mean, C, "run_mean"));
+  p.run_var = const_cast<float*>(opt_f32(run_var, C, "run_var"));
+  if (stats.has_value()) {
+    check_f32(*stats, "stats");
+    TORCH_CHECK(stats_R >= 1 && stats->dim() == 3 && stats->is_contiguous() && stats->size(0) >= stats_R &&
+                    stats->size(1) == 2 && stats_off >= 0 && stats_off + 16 <= stats->size(2),
+                "hcb.dense_conv3x3_fwd: stats must be contiguous [>= stats_R][2][>= stats_off + 16]");
+    TORCH_CHECK(stats->data_ptr() != acc.data_ptr() || stats_off >= C,
+                "hcb.dense_conv3x3_fwd: the slot's statistics columns must lie beyond the C_in columns read");
+    p.stats = stats->data_ptr<float>() + stats_off;
+    p.stats_R = (int)stats_R;
+    p.stats_C = (int)stats->size(2);
+    p.stats_shift = opt_f32(stats_shift, Nout, "stats_shift");
+  } else {
+    TORCH_CHECK(!stats_shift.has_value(), "hcb.dense_conv3x3_fwd: stats_shift without stats");
+  }
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldy = (int)ldy;
+  p.Nout = (int)Nout; p.Kpad = (int)Kpad;
+  p.x_bytes = (uint32_t)xb;
+  p.w_bytes = (uint32_t)wb;
+  hcb::launch_dense_conv3x3(p, cur_stream(), f32);
+}
+
 static int pack_mode(const Tensor& t, const char* what) {
   switch (t.scalar_type()) {
     case at::kFloat: return 0;
@@ -1804,6 +1901,10 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("shortcut_pad_bwd(Tensor g, Tensor(a!) dx, int s) -> ()");
   m.def("lrn_fwd(Tensor x, Tensor(a!) y, int r, float bias, float alpha, float beta) -> ()");
   m.def("lrn_bwd(Tensor dy, Tensor x, Tensor(a!) dx, int r, float bias, float alpha, float beta) -> ()");
+  m.def("dense_conv3x3_fwd(Tensor x, Tensor w, Tensor? w_lo, Tensor(a!) y, int[] geom, Tensor acc, int R, float eps, "
+        "float momentum, Tensor gamma, Tensor beta, Tensor? shift=None, Tensor(b!)? saved_mean=None, "
+        "Tensor(c!)? saved_invstd=None, Tensor(d!)? run_mean=None, Tensor(e!)? run_var=None, Tensor(f!)? stats=None, "
+        "int stats_R=0, int stats_off=0, Tensor? stats_shift=None) -> ()");
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
         "Tensor(e!) run_mean, Tensor(f!) run_var, Tensor? shift=None) -> ()");
@@ -1875,6 +1976,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("shortcut_pad_bwd", shortcut_pad_bwd);
   m.impl("lrn_fwd", lrn_fwd);
   m.impl("lrn_bwd", lrn_bwd);
+  m.impl("dense_conv3x3_fwd", dense_conv3x3_fwd);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);

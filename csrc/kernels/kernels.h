@@ -277,6 +277,34 @@ void launch_dwconv_dgrad(const DwParams& p, hipStream_t st, bool f32);
 int dwconv_wgrad_blocks(int N, int P, int Q, int C);
 void launch_dwconv_wgrad(const DwParams& p, float* ws, int nblk, float* dw, hipStream_t st, bool f32);
 
+// ---------------------------------------------------------------- DenseNet dense layer (dense3x3.hip)
+// y[:, 0:16] = conv3x3_SAME_s1(relu(BN(x[:, 0:C]))) in one pass: x the raw NHWC concat buffer (row stride
+// ldx; 16-bit or fp32), BN from the batch statistics in `acc` (R replicas of [2][acc_C]; channel c of
+// the buffer is column c) with the layer's gamma / beta, y the 16 channels of the layer's slot (row
+// stride ldy, x's type; channels Nout..15 are written as zeros). w: the [Nout][Kpad] pack, K = (tap, c);
+// fp32: the bf16 hi pack with w_mid / w_lo beside it.
+struct DenseParams {
+  const void* x;
+  void* y;
+  const void* w;
+  const void* w_mid;
+  const void* w_lo;
+  const float* acc;
+  int R, acc_C;
+  const float *gamma, *beta, *shift;  // [C]; shift: the K of acc's sums (null = 0)
+  float eps, momentum;
+  float *saved_mean, *saved_invstd, *run_mean, *run_var;  // [C] or null: published by block 0
+  float* stats;  // null, or column 0 of the slot in stats_R replicas of [2][stats_C]: sum(y - K), sum((y - K)^2)
+  int stats_R, stats_C;
+  const float* stats_shift;  // [Nout] or null
+  int N, H, W, C, ldx, ldy, Nout, Kpad;
+  uint32_t x_bytes, w_bytes;
+  int TR, strips_per_img, nstrips, patch_pix;  // set by the launcher
+};
+// whether the LDS budget holds a one-row strip of this width and channel count
+bool dense_conv3x3_fits(int N, int H, int W, int C, bool f32);
+void launch_dense_conv3x3(const DenseParams& p, hipStream_t st, bool f32);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

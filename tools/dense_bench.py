@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""The fused DenseNet dense-layer kernel (csrc/kernels/dense3x3.hip, Fn.dense_conv3x3_forward) against the
+unfused chain of existing kernels on the same padded layout -- bn_apply_acc writes the normalised operand
+of the C_in channels, then the conv GEMM (16 output channels) reads it back and writes the slot -- on the
+dense-layer shapes of densenet40_k12 (three blocks of 12 layers, 32 / 16 / 8 pixels, 16-channel slots), fp32
+and bf16, same machine, same process.
+
+Method (as tools/dwconv_bench.py): every form is warmed up, then timed as ITERS back-to-back launches
+between two events; the median of ROUNDS rounds is reported, the forms interleaved round by round, and the
+fused form is timed twice (A/A) so the spread of the method shows beside the ratio. Inputs are random. All
+of these layers' tensors stay in the 256 MiB Infinity Cache between launches, so the numbers are warm-cache
+ones. The unfused chain is not charged the accumulator copy it needs (its apply kernel takes statistics
+with C_in columns, the fused one the buffer's).
+
+    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from azure_hc_intel_tf_amd.nn.layers import empty_op, set_gpu_compute_dtype  # noqa: E402
+from azure_hc_intel_tf_amd.nn.params import ParamStore  # noqa: E402
+from azure_hc_intel_tf_amd.ops import functional as Fn  # noqa: E402
+from azure_hc_intel_tf_amd.ops.functional import ConvSpec  # noqa: E402
+
+K, SLOT, EPS, R = 12, Fn.DENSE_SLOT, 1e-5, 8
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters  # us
+
+
+def layer_shapes(n: int, every: bool):
+    """(H, C_in) of the dense layers: block b starts at C0 (16, then the padded width of the block before)."""
+    out, c0 = [], 16
+    for H in (32, 16, 8):
+        idx = range(n) if every else sorted({0, n // 2, n - 1})
+        out += [(H, c0 + SLOT * i) for i in idx]
+        c0 += SLOT * n
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--all", action="store_true", help="every layer (default: first, middle and last of each block)")
+    args = ap.parse_args()
+    N = args.batch
+    print(f"# batch {N}, {args.iters} launches per round, median of {args.rounds} rounds, random data, warm cache")
+    print("# dtype  H  C_in | fused us  fused(A/A) us | bn apply us + conv us = unfused us | unfused / fused | fused GB/s")
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        set_gpu_compute_dtype(dt)
+        Fn.set_f32_native(name == "fp32")
+        e = 4 if name == "fp32" else 2
+        for H, C in layer_shapes(12, args.all):
+            M = N * H * H
+            buf = torch.randn(N, H, H, C + SLOT, device="cuda").to(dt)
+            spec = ConvSpec(cin=C, cin_pad=C, cout=SLOT, kh=3, kw=3, pt=1, pl=1, pb=1, pr=1)
+            ps = ParamStore(seed=0)
+            p = ps.add("w", (SLOT, 3, 3, C), True, ps.trunc_normal((2.0 / 9 / K) ** 0.5))
+            pk = ps.add_pack(p, SLOT, 3, 3, C, spec.Kpad, spec.Kpad_t, want_tr=False)
+            ps.finalize("cuda", pack_lo=name == "fp32")
+            p.data[K:] = 0  # the pad rows
+            ps.repack()
+            gamma, beta = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
+            x = buf[..., :C].float().reshape(M, C)
+            acc = torch.zeros(R, 2, C + SLOT, device="cuda")
+            acc[:, 0, :C], acc[:, 1, :C] = x.sum(0) / R, (x * x).sum(0) / R
+            acc_c = acc[:, :, :C].contiguous()
+            acc_o = torch.zeros(R, 2, SLOT, device="cuda")
+            sv = torch.empty(2, C, device="cuda")
+            op = empty_op((N, H, H, C), "cuda")  # the normalised operand of the unfused chain (Planes on fp32)
+            slot = buf[..., C:C + SLOT]
+
+            def fused():
+                Fn.dense_conv3x3_forward(buf, C, C, p.data[:K], gamma, beta, EPS, acc=acc, R=R, saved_mean=sv[0],
+                                         saved_invstd=sv[1], stats=acc, stats_R=R, wpack=pk.pack)
+
+            def bn():
+                Fn.bn_forward_acc(buf[..., :C], gamma, beta, None, None, 1.0, EPS, op, True, acc_c, R, sv[0], sv[1])
+
+            def conv():
+                Fn.conv_forward(op, spec, pk.pack, p.data, slot, stats=acc_o, stats_R=R)
+
+            ops = {"fused": fused, "fused2": fused, "bn": bn, "conv": conv}
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            m = {k: statistics.median(v) for k, v in t.items()}
+            un = m["bn"] + m["conv"]
+            gbs = M * (C + SLOT) * e / (m["fused"] * 1e-6) / 1e9  # algorithmic bytes: the input once, the slot once
+            print(f"{name:5s} {H:3d} {C:5d} | {m['fused']:8.1f} {m['fused2']:8.1f} | {m['bn']:8.1f} + {m['conv']:8.1f} = "
+                  f"{un:8.1f} | {un / m['fused']:5.2f} | {gbs:6.0f}")
+    Fn.set_f32_native(False)
+    set_gpu_compute_dtype(torch.bfloat16)
+
+
+if __name__ == "__main__":
+    main()
