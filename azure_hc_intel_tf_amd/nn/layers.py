@@ -1023,6 +1023,10 @@ class Logits(Layer):
 # dense3x3.hip, Fn.dense_conv3x3_forward). False: bn_apply_acc writes the normalised operand and the
 # existing conv GEMM (16 output columns) writes the slot, on the same layout -- the A/B partner
 FUSE_DENSE = _env_on("HCB_FUSE_DENSE")
+# The dense layers' weight gradient with BN and ReLU applied on the way in (csrc/kernels/dense3x3_wgrad.hip,
+# Fn.dense_conv3x3_wgrad): no re-materialised operand, no scratch for it. False: bn_apply_acc writes the
+# operand and conv_wgrad reads it back -- the A/B partner. Independent of FUSE_DENSE (profiles/densenet_wgrad.txt)
+FUSE_DENSE_WGRAD = _env_on("HCB_FUSE_DENSE_WGRAD")
 
 
 def dense_channel_mask(c0: int, n: int, k: int) -> torch.Tensor:
@@ -1091,10 +1095,11 @@ class DenseBlock(Layer):
     ``input_view`` (no copy); ``forward`` returns the whole buffer [N, H, W, c0 + 16 n]. The buffer's batch
     statistics live in one accumulator (R replicas of [2][c_total]): the input's columns from bn_stats_acc,
     each slot's from the kernel that produced it, read by every later layer -- nothing is reduced twice.
-    Backward (existing kernels on the padded layout): per layer, last to first, the normalised operand is
-    re-materialised by bn_apply_acc into a scratch shared by the block, the weight- and data-gradient GEMMs
-    run with 16 output columns on the layer's slot of the gradient buffer, and the BN backward adds into
-    the first c_in channels of that same gradient buffer (bn_bwd_apply_acc's ``add``)."""
+    Backward, per layer, last to first: the weight gradient normalises its operand on the way into LDS
+    (FUSE_DENSE_WGRAD: Fn.dense_conv3x3_wgrad, one workspace per block) -- or, switch off, the operand is
+    re-materialised by bn_apply_acc into a scratch shared by the block and conv_wgrad reads it back; the
+    data-gradient GEMM runs with 16 output columns on the layer's slot of the gradient buffer, and the BN
+    backward adds into the first c_in channels of that same gradient buffer (bn_bwd_apply_acc's ``add``)."""
 
     def __init__(self, ps: ParamStore, name: str, in_shape, n: int, k: int = 12, eps: float = 1e-5,
                  decay: float = 0.9):
@@ -1182,16 +1187,27 @@ class DenseBlock(Layer):
         N, H, W, _ = buf.shape
         S, dev = Fn.DENSE_SLOT, buf.device
         cmax = self.subs[-1].c_in
-        op_all, da_all = empty_op((N, H, W, cmax), dev), empty_act((N, H, W, cmax), dev)
+        fuse = FUSE_DENSE_WGRAD
+        da_all = empty_act((N, H, W, cmax), dev)
+        if fuse:  # one workspace per block, sized for the layer that needs the most
+            ws = Fn.dense_wgrad_workspace(buf.shape, [L.c_in for L in self.subs], buf.dtype, dev)
+        else:
+            op_all = empty_op((N, H, W, cmax), dev)
         for L in reversed(self.subs):
             c = L.c_in
-            x, op, da, Gin = buf[..., :c], op_all[..., :c], da_all[..., :c], G[..., :c]
-            Fn.bn_forward_acc(x, L.gamma.data, L.beta.data, None, None, 1.0, self.eps, op, True,
-                              acc[:, :, :c].contiguous(), R, L.sv_mean.data, L.sv_invstd.data, shift=self._sh(0, c))
+            x, da, Gin = buf[..., :c], da_all[..., :c], G[..., :c]
             dz = G[..., L.slot:L.slot + S]
+            if fuse:
+                Fn.dense_conv3x3_wgrad(buf, c, dz, L.gamma.data, L.beta.data, L.sv_mean.data, L.sv_invstd.data,
+                                       L.w.grad.view(S, -1), self.k, ws=ws)
+            else:
+                op = op_all[..., :c]
+                Fn.bn_forward_acc(x, L.gamma.data, L.beta.data, None, None, 1.0, self.eps, op, True,
+                                  acc[:, :, :c].contiguous(), R, L.sv_mean.data, L.sv_invstd.data, shift=self._sh(0, c))
             if Fn.planes_mode():
                 dz = Fn.to_planes(dz)  # one split for both GEMMs
-            Fn.conv_wgrad(dz, op, L.spec, L.w.grad.view(S, -1))
+            if not fuse:
+                Fn.conv_wgrad(dz, op, L.spec, L.w.grad.view(S, -1))
             Fn.conv_dgrad(dz, L.spec, L.pack.tr, L.w.data, da, False)
             acc_b = (torch.zeros((R, 2, c), dtype=torch.float32, device=dev) if Fn.deterministic() else L.acc_b.data)
             Fn.bn_backward_acc(da, None, x, Fn.BNSaved(L.sv_mean.data, L.sv_invstd.data), L.gamma.data, L.beta.data, 2,

@@ -1625,6 +1625,54 @@ def dense_conv3x3_forward(buf, c_in: int, slot: int, w, gamma, beta, eps: float,
     return buf
 
 
+def dense_wgrad_workspace(shape, c_in, dtype, device):
+    """The caller-owned workspace of dense_conv3x3_wgrad for a buffer of ``shape`` [N, H, W, ld] read up to
+    ``c_in`` channels: [slabs * 16 * 9 * round_up(c_in, 32)] fp32, never zeroed. The slab count depends on
+    the problem alone and falls as the chunks grow in number, so the need is not monotonic in ``c_in``: give
+    every ``c_in`` of a block (an iterable) for one workspace that serves all of its layers."""
+    N, H, W = shape[:3]
+    cs = [c_in] if isinstance(c_in, int) else list(c_in)
+    n = max(_ext.ops().dense_conv3x3_wgrad_ws([N, H, W, c, c, 0, DENSE_SLOT, DENSE_SLOT], dtype == torch.float32)
+            for c in cs)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def dense_conv3x3_wgrad(buf, c_in: int, dz, gamma, beta, saved_mean, saved_invstd, dw, nout: int, ws=None):
+    """The weight gradient of one DenseNet layer, with its BatchNorm and ReLU applied on the way in:
+
+        dw[n, r, s, c] += sum_{img, oh, ow} dz[img, oh, ow, n] * a[img, oh + r - 1, ow + s - 1, c],   n < nout
+        a = relu(x * sc + sh),  sc = gamma * invstd,  sh = beta - mean * sc,  a = 0 outside the image
+
+    ``buf`` [N, H, W, ld]: the block's raw concat buffer, x = buf[..., :c_in]; ``dz`` [N, H, W, 16]: the layer's
+    slot of the block's gradient buffer (a channel-slice view; buf's dtype); ``saved_mean`` / ``saved_invstd``: the
+    batch statistics the forward published; ``dw``: fp32 [16, 9 * c_in] (conv_wgrad's layout), added into; rows
+    nout..15 are left alone.
+
+    GPU (csrc/kernels/dense3x3_wgrad.hip): two launches, the normalised operand is never written; per-slab
+    partials go through ``ws`` (dense_wgrad_workspace) and are folded in slab order, so the result is
+    bitwise reproducible in every mode. 16-bit or plain fp32 tensors (not Planes). CPU / non-native tensors:
+    the formula above in PyTorch at ``buf``'s dtype (torch.nn.grad.conv2d_weight on the normalised map),
+    which is the definition."""
+    N, H, W, _ = buf.shape
+    assert nout <= DENSE_SLOT and tuple(dz.shape) == (N, H, W, DENSE_SLOT), "dense_conv3x3_wgrad: dz is the 16-channel slot"
+    if native(buf):
+        assert not is_planes(buf) and not is_planes(dz), "the dense-layer kernels read plain tensors"
+        if ws is None:
+            ws = dense_wgrad_workspace(buf.shape, c_in, buf.dtype, buf.device)
+        slot = dz.storage_offset() % ld(dz)  # the view's first channel inside its rows
+        _ext.ops().dense_conv3x3_wgrad(buf, dz, gamma, beta, saved_mean, saved_invstd, ws, dw,
+                                       [N, H, W, c_in, ld(buf), slot, ld(dz), nout])
+        return dw
+    dt = buf.dtype
+    sc = (saved_invstd[:c_in] * gamma[:c_in]).to(dt)
+    sh = (beta[:c_in] - saved_mean[:c_in] * saved_invstd[:c_in] * gamma[:c_in]).to(dt)
+    a = torch.relu(buf[..., :c_in] * sc + sh)
+    g = torch.nn.grad.conv2d_weight(a.permute(0, 3, 1, 2), (nout, c_in, 3, 3),
+                                    dz[..., :nout].to(dt).permute(0, 3, 1, 2), padding=1)
+    dw[:nout, :9 * c_in] += g.permute(0, 2, 3, 1).reshape(nout, 9 * c_in).to(dw.dtype)
+    return dw
+
+
 # ------------------------------------------------------------------------- loss
 def softmax_xent(logits, labels, ncls, row_loss, dlogits, scale, scale_dev=None, dl32=None,
                  label_smoothing: float = 0.0):

@@ -1594,6 +1594,73 @@ void dense_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Ten
   hcb::launch_dense_conv3x3(p, cur_stream(), f32);
 }
 
+// ---- dense layer weight gradient (dense3x3_wgrad.hip): dw[n][tap * C + c] += sum dz[.., slot + n] *
+// relu(BN(x[.., c])) shifted by the tap. geom = [N, H, W, C, ldx, slot, ldz, Nout]: x the raw NHWC concat
+// buffer, dz the layer's 16 channels of the block's gradient buffer (a view: rows of ldz channels, the
+// view starting at channel `slot` of them), mean / invstd the saved batch statistics, ws the workspace of dense_conv3x3_wgrad_ws floats (never zeroed), dw fp32
+// [16][>= 9 * C] (rows Nout..15 untouched)
+static hcb::DenseWgradPlan dense_wgrad_plan(at::IntArrayRef g, bool f32) {
+  TORCH_CHECK(g.size() == 8, "hcb.dense_conv3x3_wgrad: geom = [N, H, W, C, ldx, slot, ldz, Nout]");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3];
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.dense_conv3x3_wgrad: empty tensor");
+  TORCH_CHECK(C >= 8 && C % 8 == 0, "hcb.dense_conv3x3_wgrad: C_in must be a multiple of 8, got ", C);
+  TORCH_CHECK(C <= 2048, "hcb.dense_conv3x3_wgrad: C_in <= 2048 (the BatchNorm kernels' limit), got ", C);
+  TORCH_CHECK(N * H * W < (1ll << 31), "hcb.dense_conv3x3_wgrad: tensors must stay below 2 GiB (32-bit offsets)");
+  hcb::DenseWgradPlan pl;
+  TORCH_CHECK(W <= (1 << 20) && hcb::dense_conv3x3_wgrad_plan((int)N, (int)H, (int)W, (int)C, f32, &pl),
+              "hcb.dense_conv3x3_wgrad: W = ", W, " is larger than the input patch the LDS budget allows");
+  return pl;
+}
+
+int64_t dense_conv3x3_wgrad_ws(at::IntArrayRef g, bool f32) { return dense_wgrad_plan(g, f32).ws_floats; }
+
+void dense_conv3x3_wgrad(const Tensor& x, const Tensor& dz, const Tensor& gamma, const Tensor& beta, const Tensor& mean,
+                         const Tensor& invstd, const Tensor& ws, const Tensor& dw, at::IntArrayRef g) {
+  const bool f32 = check_act_or_f32(x, "x");
+  check_cuda(dz, "dz");
+  TORCH_CHECK(dz.scalar_type() == x.scalar_type(), "hcb.dense_conv3x3_wgrad: x and dz dtypes differ");
+  const hcb::DenseWgradPlan pl = dense_wgrad_plan(g, f32);
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], slot = g[5], ldz = g[6], Nout = g[7];
+  const int64_t e = f32 ? 4 : 2;
+  TORCH_CHECK(slot >= 0 && slot % 8 == 0, "hcb.dense_conv3x3_wgrad: the slot offset must be a multiple of 8, got ", slot);
+  TORCH_CHECK(ldx % 8 == 0 && ldz % 8 == 0, "hcb.dense_conv3x3_wgrad: ld must be a multiple of 8, got ", ldx, " / ", ldz);
+  TORCH_CHECK(ldx >= C && ldz >= slot + 16, "hcb.dense_conv3x3_wgrad: rows of ", ldx, " / ", ldz,
+              " channels do not hold C_in = ", C, " / the slot at ", slot);
+  TORCH_CHECK(Nout >= 1 && Nout <= 16, "hcb.dense_conv3x3_wgrad: Nout <= 16 (one MFMA tile of output channels), got ", Nout);
+  TORCH_CHECK(x.stride(-1) == 1 && dz.stride(-1) == 1,
+              "hcb.dense_conv3x3_wgrad: non-contiguous rows (channel stride must be 1)");
+  const int64_t M = N * H * W;
+  const int64_t xb = ((M - 1) * ldx + C) * e, zb = ((M - 1) * ldz + 16) * e;
+  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31), "hcb.dense_conv3x3_wgrad: tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(dz, zb, "dz");
+  check_align16(x.data_ptr(), "x");
+  check_align16(dz.data_ptr(), "dz");
+  check_cuda(dw, "dw");
+  TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.dim() == 2 && dw.size(0) == 16 && dw.stride(1) == 1 &&
+                  dw.size(1) >= 9 * C && dw.stride(0) >= 9 * C,
+              "hcb.dense_conv3x3_wgrad: dw must be float32 [16][>= 9 * C_in] with contiguous rows of stride >= 9 * C_in");
+  check_range(dw, (15 * dw.stride(0) + 9 * C) * 4, "dw");
+  check_cuda(ws, "ws");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= pl.ws_floats,
+              "hcb.dense_conv3x3_wgrad: the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ",
+              pl.ws_floats, " (dense_conv3x3_wgrad_ws)");
+  hcb::DenseWgradParams p{};
+  p.x = x.data_ptr();
+  p.dz = dz.data_ptr();
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.mean = opt_f32(mean, C, "saved_mean");
+  p.invstd = opt_f32(invstd, C, "saved_invstd");
+  p.ws = ws.data_ptr<float>();
+  p.dw = dw.data_ptr<float>();
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldz = (int)ldz;
+  p.Nout = (int)Nout; p.ldw = (int)dw.stride(0);
+  p.x_bytes = (uint32_t)xb;
+  p.dz_bytes = (uint32_t)zb;
+  hcb::launch_dense_conv3x3_wgrad(p, cur_stream(), f32);
+}
+
 static int pack_mode(const Tensor& t, const char* what) {
   switch (t.scalar_type()) {
     case at::kFloat: return 0;
@@ -1905,6 +1972,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
         "float momentum, Tensor gamma, Tensor beta, Tensor? shift=None, Tensor(b!)? saved_mean=None, "
         "Tensor(c!)? saved_invstd=None, Tensor(d!)? run_mean=None, Tensor(e!)? run_var=None, Tensor(f!)? stats=None, "
         "int stats_R=0, int stats_off=0, Tensor? stats_shift=None) -> ()");
+  m.def("dense_conv3x3_wgrad(Tensor x, Tensor dz, Tensor gamma, Tensor beta, Tensor saved_mean, Tensor saved_invstd, "
+        "Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
+  m.def("dense_conv3x3_wgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_wgrad_ws);
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
         "Tensor(e!) run_mean, Tensor(f!) run_var, Tensor? shift=None) -> ()");
@@ -1977,6 +2047,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("lrn_fwd", lrn_fwd);
   m.impl("lrn_bwd", lrn_bwd);
   m.impl("dense_conv3x3_fwd", dense_conv3x3_fwd);
+  m.impl("dense_conv3x3_wgrad", dense_conv3x3_wgrad);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);

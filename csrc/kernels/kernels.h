@@ -305,6 +305,33 @@ struct DenseParams {
 bool dense_conv3x3_fits(int N, int H, int W, int C, bool f32);
 void launch_dense_conv3x3(const DenseParams& p, hipStream_t st, bool f32);
 
+// ---------------------------------------------------------------- dense layer weight gradient (dense3x3_wgrad.hip)
+// dw[n][tap * C + c] += sum over pixels of dz[pixel][n] * relu(BN(x))[pixel + tap][c] (3x3, SAME, stride 1),
+// BN and ReLU applied on the way into LDS: x the raw NHWC concat buffer (row stride ldx), dz column 0 of the
+// layer's 16-channel slot of the gradient buffer (row stride ldz, x's type), mean / invstd the saved batch
+// statistics. Two launches without atomics: per (32-channel chunk, pixel slab) partials into ws
+// [nslabs][16][9][C rounded up to 32] (caller-owned, never zeroed, every element read is written first),
+// then a fold in slab order that adds rows 0 .. Nout - 1 into dw (fp32, row stride ldw >= 9 * C).
+struct DenseWgradParams {
+  const void* x;
+  const void* dz;
+  const float *gamma, *beta, *mean, *invstd;  // [C]
+  float* ws;
+  float* dw;
+  int N, H, W, C, ldx, ldz, Nout, ldw;
+  uint32_t x_bytes, dz_bytes;
+  int TR, patch_pix, strips_per_img, nstrips, strips_per_slab, nslabs;  // set by the launcher
+};
+struct DenseWgradPlan {
+  int TR, patch_pix, strips_per_img, nstrips, strips_per_slab, nslabs;
+  size_t lds_bytes;
+  int64_t ws_floats;
+};
+// strip rows, slab count and workspace floats of this problem (a function of the shape alone); false when
+// even one-row strips of this width do not fit the LDS budget
+bool dense_conv3x3_wgrad_plan(int N, int H, int W, int C, bool f32, DenseWgradPlan* out);
+void launch_dense_conv3x3_wgrad(const DenseWgradParams& p, hipStream_t st, bool f32);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

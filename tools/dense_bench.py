@@ -12,7 +12,12 @@ of these layers' tensors stay in the 256 MiB Infinity Cache between launches, so
 ones. The unfused chain is not charged the accumulator copy it needs (its apply kernel takes statistics
 with C_in columns, the fused one the buffer's).
 
-    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all]
+--wgrad times the weight gradient of the same layers instead: the fused kernel (csrc/kernels/dense3x3_wgrad.hip,
+Fn.dense_conv3x3_wgrad: two launches, partials + fold) against bn_apply_acc re-materialising the operand and
+conv_wgrad reading it back, by the same method (the unfused chain is again not charged its accumulator copy,
+nor the fp32 path's split of dz, which the data gradient needs either way).
+
+    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all] [--wgrad]
 """
 import argparse
 import os
@@ -50,13 +55,68 @@ def layer_shapes(n: int, every: bool):
     return out
 
 
+def wgrad_main(args):
+    N = args.batch
+    print(f"# weight gradient: batch {N}, {args.iters} launches per round, median of {args.rounds} rounds, random data, "
+          "warm cache")
+    print("# dtype  H  C_in | fused us  fused(A/A) us | bn apply us + wgrad us = unfused us | unfused / fused | fused GB/s")
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        set_gpu_compute_dtype(dt)
+        Fn.set_f32_native(name == "fp32")
+        e = 4 if name == "fp32" else 2
+        for H, C in layer_shapes(12, args.all):
+            M = N * H * H
+            buf = torch.randn(N, H, H, C + SLOT, device="cuda").to(dt)
+            G = torch.randn(N, H, H, C + SLOT, device="cuda").to(dt)
+            spec = ConvSpec(cin=C, cin_pad=C, cout=SLOT, kh=3, kw=3, pt=1, pl=1, pb=1, pr=1)
+            gamma, beta = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
+            x = buf[..., :C].float().reshape(M, C)
+            acc_c = torch.zeros(R, 2, C, device="cuda")
+            acc_c[:, 0], acc_c[:, 1] = x.sum(0) / R, (x * x).sum(0) / R
+            sv = torch.empty(2, C, device="cuda")
+            op = empty_op((N, H, H, C), "cuda")
+            dw = torch.zeros(SLOT, 9 * C, device="cuda")
+            ws = Fn.dense_wgrad_workspace(buf.shape, C, dt, "cuda")
+            dz = G[..., C:]
+            dzp = Fn.to_planes(dz) if name == "fp32" else dz
+
+            def bn():
+                Fn.bn_forward_acc(buf[..., :C], gamma, beta, None, None, 1.0, EPS, op, True, acc_c, R, sv[0], sv[1])
+
+            def fused():
+                Fn.dense_conv3x3_wgrad(buf, C, dz, gamma, beta, sv[0], sv[1], dw, K, ws=ws)
+
+            def wgrad():
+                Fn.conv_wgrad(dzp, op, spec, dw)
+
+            ops = {"bn": bn, "fused": fused, "fused2": fused, "conv": wgrad}
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            m = {k: statistics.median(v) for k, v in t.items()}
+            un = m["bn"] + m["conv"]
+            gbs = M * (C + SLOT) * e / (m["fused"] * 1e-6) / 1e9  # algorithmic bytes: the input once, the slot once
+            print(f"{name:5s} {H:3d} {C:5d} | {m['fused']:8.1f} {m['fused2']:8.1f} | {m['bn']:8.1f} + {m['conv']:8.1f} = "
+                  f"{un:8.1f} | {un / m['fused']:5.2f} | {gbs:6.0f}", flush=True)
+    Fn.set_f32_native(False)
+    set_gpu_compute_dtype(torch.bfloat16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--all", action="store_true", help="every layer (default: first, middle and last of each block)")
+    ap.add_argument("--wgrad", action="store_true", help="the weight gradient instead of the forward pass")
     args = ap.parse_args()
+    if args.wgrad:
+        return wgrad_main(args)
     N = args.batch
     print(f"# batch {N}, {args.iters} launches per round, median of {args.rounds} rounds, random data, warm cache")
     print("# dtype  H  C_in | fused us  fused(A/A) us | bn apply us + conv us = unfused us | unfused / fused | fused GB/s")
