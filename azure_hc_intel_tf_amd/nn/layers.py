@@ -1027,6 +1027,12 @@ FUSE_DENSE = _env_on("HCB_FUSE_DENSE")
 # Fn.dense_conv3x3_wgrad): no re-materialised operand, no scratch for it. False: bn_apply_acc writes the
 # operand and conv_wgrad reads it back -- the A/B partner. Independent of FUSE_DENSE (profiles/densenet_wgrad.txt)
 FUSE_DENSE_WGRAD = _env_on("HCB_FUSE_DENSE_WGRAD")
+# The dense layers' data gradient with the ReLU and BatchNorm backward applied in registers (csrc/kernels/
+# dense3x3_dgrad.hip, Fn.dense_conv3x3_dgrad): the gradient of the normalised operand is never stored, no scratch
+# for it, no backward statistics accumulator. False: conv_dgrad writes it and bn_backward_acc reads it twice --
+# the A/B partner. Independent of FUSE_DENSE and FUSE_DENSE_WGRAD. Default OFF (``HCB_FUSE_DENSE_DGRAD=1`` turns
+# it on): the captured step measured no gain in fp32 and a loss in bf16 (profiles/densenet_dgrad.txt)
+FUSE_DENSE_DGRAD = os.environ.get("HCB_FUSE_DENSE_DGRAD", "0") == "1"
 
 
 def dense_channel_mask(c0: int, n: int, k: int) -> torch.Tensor:
@@ -1097,9 +1103,12 @@ class DenseBlock(Layer):
     each slot's from the kernel that produced it, read by every later layer -- nothing is reduced twice.
     Backward, per layer, last to first: the weight gradient normalises its operand on the way into LDS
     (FUSE_DENSE_WGRAD: Fn.dense_conv3x3_wgrad, one workspace per block) -- or, switch off, the operand is
-    re-materialised by bn_apply_acc into a scratch shared by the block and conv_wgrad reads it back; the
-    data-gradient GEMM runs with 16 output columns on the layer's slot of the gradient buffer, and the BN
-    backward adds into the first c_in channels of that same gradient buffer (bn_bwd_apply_acc's ``add``)."""
+    re-materialised by bn_apply_acc into a scratch shared by the block and conv_wgrad reads it back. The data
+    gradient, the ReLU mask and the BN backward run as one op that adds into the first c_in channels of the
+    gradient buffer and never stores the operand's gradient (FUSE_DENSE_DGRAD: Fn.dense_conv3x3_dgrad, one
+    workspace per block) -- or, switch off, the data-gradient GEMM runs with 16 output columns on the layer's
+    slot of the gradient buffer into a scratch shared by the block, and the BN backward reads it back and adds
+    into that same gradient buffer (bn_bwd_apply_acc's ``add``)."""
 
     def __init__(self, ps: ParamStore, name: str, in_shape, n: int, k: int = 12, eps: float = 1e-5,
                  decay: float = 0.9):
@@ -1187,15 +1196,18 @@ class DenseBlock(Layer):
         N, H, W, _ = buf.shape
         S, dev = Fn.DENSE_SLOT, buf.device
         cmax = self.subs[-1].c_in
-        fuse = FUSE_DENSE_WGRAD
-        da_all = empty_act((N, H, W, cmax), dev)
+        fuse, fuse_d = FUSE_DENSE_WGRAD, FUSE_DENSE_DGRAD
+        if fuse_d:
+            ws_d = Fn.dense_dgrad_workspace(buf.shape, [L.c_in for L in self.subs], buf.dtype, dev)
+        else:
+            da_all = empty_act((N, H, W, cmax), dev)
         if fuse:  # one workspace per block, sized for the layer that needs the most
             ws = Fn.dense_wgrad_workspace(buf.shape, [L.c_in for L in self.subs], buf.dtype, dev)
         else:
             op_all = empty_op((N, H, W, cmax), dev)
         for L in reversed(self.subs):
             c = L.c_in
-            x, da, Gin = buf[..., :c], da_all[..., :c], G[..., :c]
+            x, Gin = buf[..., :c], G[..., :c]
             dz = G[..., L.slot:L.slot + S]
             if fuse:
                 Fn.dense_conv3x3_wgrad(buf, c, dz, L.gamma.data, L.beta.data, L.sv_mean.data, L.sv_invstd.data,
@@ -1204,6 +1216,13 @@ class DenseBlock(Layer):
                 op = op_all[..., :c]
                 Fn.bn_forward_acc(x, L.gamma.data, L.beta.data, None, None, 1.0, self.eps, op, True,
                                   acc[:, :, :c].contiguous(), R, L.sv_mean.data, L.sv_invstd.data, shift=self._sh(0, c))
+            if fuse_d:  # (no Planes of dz unless the unfused weight gradient wants them)
+                if not fuse:
+                    Fn.conv_wgrad(Fn.to_planes(dz) if Fn.planes_mode() else dz, op, L.spec, L.w.grad.view(S, -1))
+                Fn.dense_conv3x3_dgrad(buf, c, dz, L.w.data, L.gamma.data, L.beta.data, L.sv_mean.data, L.sv_invstd.data,
+                                       Gin, L.gamma.grad, L.beta.grad, self.k, ws=ws_d)
+                continue
+            da = da_all[..., :c]
             if Fn.planes_mode():
                 dz = Fn.to_planes(dz)  # one split for both GEMMs
             if not fuse:

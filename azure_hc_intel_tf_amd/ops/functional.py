@@ -1673,6 +1673,65 @@ def dense_conv3x3_wgrad(buf, c_in: int, dz, gamma, beta, saved_mean, saved_invst
     return dw
 
 
+def dense_dgrad_workspace(shape, c_in, dtype, device):
+    """The caller-owned workspace of dense_conv3x3_dgrad for a buffer of ``shape`` [N, H, W, ld] read up to
+    ``c_in`` channels: [slabs * 2 * round_up(c_in, 32)] fp32, never zeroed. As with dense_wgrad_workspace the
+    need is not monotonic in ``c_in``: give every ``c_in`` of a block (an iterable) for one workspace that
+    serves all of its layers."""
+    N, H, W = shape[:3]
+    cs = [c_in] if isinstance(c_in, int) else list(c_in)
+    n = max(_ext.ops().dense_conv3x3_dgrad_ws([N, H, W, c, c, DENSE_SLOT, c, DENSE_SLOT], dtype == torch.float32)
+            for c in cs)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def dense_conv3x3_dgrad(buf, c_in: int, dz, w, gamma, beta, saved_mean, saved_invstd, gin, dgamma, dbeta, nout: int,
+                        ws=None):
+    """The data gradient of one DenseNet layer pushed through its ReLU and BatchNorm, added into ``gin``:
+
+        da[i, h, v, c] = sum_{r, s, n < nout} dz[i, h + 1 - r, v + 1 - s, n] * w[n, r, s, c]     (dz = 0 outside the image)
+        g = da where x * sc + sh > 0 else 0,   sc = gamma * invstd,  sh = beta - mean * sc,   x = buf[..., :c_in]
+        dbeta[c] = sum_pixels g,   dgamma[c] = sum_pixels g * xhat,   xhat = (x - mean) * invstd
+        gin += sc * (g - dbeta / M - xhat * dgamma / M)
+
+    ``buf`` [N, H, W, ld]: the block's raw concat buffer; ``dz`` [N, H, W, 16]: the layer's slot of the block's
+    gradient buffer and ``gin`` [N, H, W, c_in] its first c_in channels (channel-slice views of one buffer whose
+    slot lies at or beyond c_in, or separate tensors; buf's dtype); ``w``: the fp32 master kernel
+    [>= nout, 3, 3, c_in]; ``saved_mean`` / ``saved_invstd``: the batch statistics the forward published;
+    ``dgamma`` / ``dbeta``: fp32 [>= c_in], overwritten.
+
+    GPU (csrc/kernels/dense3x3_dgrad.hip): three launches (reduce, fold, apply); da is recomputed in registers by
+    both passes and never stored, the per-slab sums go through ``ws`` (dense_dgrad_workspace) and are folded in
+    slab order, so the result is bitwise reproducible in every mode. 16-bit or plain fp32 tensors (not Planes).
+    CPU / non-native tensors: the formula above in PyTorch at ``buf``'s dtype, which is the definition."""
+    N, H, W, _ = buf.shape
+    assert nout <= DENSE_SLOT and tuple(dz.shape) == (N, H, W, DENSE_SLOT), "dense_conv3x3_dgrad: dz is the 16-channel slot"
+    assert tuple(gin.shape) == (N, H, W, c_in) and tuple(w.shape[1:]) == (3, 3, c_in), \
+        "dense_conv3x3_dgrad: gin is [N, H, W, c_in], w [nout.., 3, 3, c_in]"
+    if native(buf):
+        assert not is_planes(buf) and not is_planes(dz) and not is_planes(gin), "the dense-layer kernels take plain tensors"
+        if ws is None:
+            ws = dense_dgrad_workspace(buf.shape, c_in, buf.dtype, buf.device)
+        _ext.ops().dense_conv3x3_dgrad(buf, dz, gin, w, gamma, beta, saved_mean, saved_invstd, ws, dgamma, dbeta,
+                                       [N, H, W, c_in, ld(buf), ld(dz), ld(gin), nout])
+        return gin
+    dt = buf.dtype
+    M = N * H * W
+    x = buf[..., :c_in]
+    mean, invstd = saved_mean[:c_in].to(dt), saved_invstd[:c_in].to(dt)
+    sc = (saved_invstd[:c_in] * gamma[:c_in]).to(dt)
+    sh = (beta[:c_in] - saved_mean[:c_in] * saved_invstd[:c_in] * gamma[:c_in]).to(dt)
+    da = F.conv_transpose2d(dz[..., :nout].to(dt).permute(0, 3, 1, 2), w[:nout].to(dt).permute(0, 3, 1, 2),
+                            padding=1).permute(0, 2, 3, 1)
+    g = torch.where(x * sc + sh > 0, da, torch.zeros_like(da))
+    xhat = (x - mean) * invstd
+    db, dg = g.sum((0, 1, 2)), (g * xhat).sum((0, 1, 2))
+    gin += sc * (g - db / M - xhat * dg / M)
+    dbeta[:c_in] = db.to(dbeta.dtype)
+    dgamma[:c_in] = dg.to(dgamma.dtype)
+    return gin
+
+
 # ------------------------------------------------------------------------- loss
 def softmax_xent(logits, labels, ncls, row_loss, dlogits, scale, scale_dev=None, dl32=None,
                  label_smoothing: float = 0.0):

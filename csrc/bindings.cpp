@@ -1661,6 +1661,92 @@ void dense_conv3x3_wgrad(const Tensor& x, const Tensor& dz, const Tensor& gamma,
   hcb::launch_dense_conv3x3_wgrad(p, cur_stream(), f32);
 }
 
+// ---- dense layer data gradient with the ReLU / BatchNorm backward applied in registers (dense3x3_dgrad.hip):
+// gin += BN-backward(relu'(BN(x)) * conv3x3-dgrad(dz, w)), dgamma / dbeta overwritten. geom = [N, H, W, C, ldx,
+// ldz, ldg, Nout]: x the raw NHWC concat buffer, dz the layer's 16 channels of the block's gradient buffer and gin
+// its first C channels (views: rows of ldz / ldg channels), w the fp32 master kernel [>= Nout][3][3][C], mean /
+// invstd the saved batch statistics, ws the workspace of dense_conv3x3_dgrad_ws floats (never zeroed)
+static hcb::DenseDgradPlan dense_dgrad_plan(at::IntArrayRef g, bool f32) {
+  TORCH_CHECK(g.size() == 8, "hcb.dense_conv3x3_dgrad: geom = [N, H, W, C, ldx, ldz, ldg, Nout]");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3];
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.dense_conv3x3_dgrad: empty tensor");
+  TORCH_CHECK(C >= 8 && C % 8 == 0, "hcb.dense_conv3x3_dgrad: C_in must be a multiple of 8, got ", C);
+  TORCH_CHECK(C <= 2048, "hcb.dense_conv3x3_dgrad: C_in <= 2048 (the BatchNorm kernels' limit), got ", C);
+  TORCH_CHECK(N * H * W < (1ll << 31), "hcb.dense_conv3x3_dgrad: tensors must stay below 2 GiB (32-bit offsets)");
+  hcb::DenseDgradPlan pl;
+  TORCH_CHECK(W <= (1 << 20) && hcb::dense_conv3x3_dgrad_plan((int)N, (int)H, (int)W, (int)C, f32, &pl),
+              "hcb.dense_conv3x3_dgrad: W = ", W, " is larger than the dz patch the LDS budget allows");
+  return pl;
+}
+
+int64_t dense_conv3x3_dgrad_ws(at::IntArrayRef g, bool f32) { return dense_dgrad_plan(g, f32).ws_floats; }
+
+void dense_conv3x3_dgrad(const Tensor& x, const Tensor& dz, const Tensor& gin, const Tensor& w, const Tensor& gamma,
+                         const Tensor& beta, const Tensor& mean, const Tensor& invstd, const Tensor& ws,
+                         const Tensor& dgamma, const Tensor& dbeta, at::IntArrayRef g) {
+  const bool f32 = check_act_or_f32(x, "x");
+  check_cuda(dz, "dz");
+  check_cuda(gin, "gin");
+  TORCH_CHECK(dz.scalar_type() == x.scalar_type() && gin.scalar_type() == x.scalar_type(),
+              "hcb.dense_conv3x3_dgrad: x, dz and gin dtypes differ");
+  const hcb::DenseDgradPlan pl = dense_dgrad_plan(g, f32);
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], ldz = g[5], ldg = g[6], Nout = g[7];
+  const int64_t e = f32 ? 4 : 2;
+  TORCH_CHECK(ldx % 8 == 0 && ldz % 8 == 0 && ldg % 8 == 0, "hcb.dense_conv3x3_dgrad: ld must be a multiple of 8, got ",
+              ldx, " / ", ldz, " / ", ldg);
+  TORCH_CHECK(ldx >= C && ldz >= 16 && ldg >= C, "hcb.dense_conv3x3_dgrad: rows of ", ldx, " / ", ldz, " / ", ldg,
+              " channels do not hold C_in = ", C, " / the 16-channel slot");
+  TORCH_CHECK(Nout >= 1 && Nout <= 16, "hcb.dense_conv3x3_dgrad: Nout <= 16 (one MFMA tile of output channels), got ", Nout);
+  TORCH_CHECK(x.stride(-1) == 1 && dz.stride(-1) == 1 && gin.stride(-1) == 1,
+              "hcb.dense_conv3x3_dgrad: non-contiguous rows (channel stride must be 1)");
+  const int64_t M = N * H * W;
+  const int64_t xb = ((M - 1) * ldx + C) * e, zb = ((M - 1) * ldz + 16) * e, gb = ((M - 1) * ldg + C) * e;
+  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31) && gb < (1ll << 31),
+              "hcb.dense_conv3x3_dgrad: tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(dz, zb, "dz");
+  check_range(gin, gb, "gin");
+  check_align16(x.data_ptr(), "x");
+  check_align16(dz.data_ptr(), "dz");
+  check_align16(gin.data_ptr(), "gin");
+  // gin is updated while other workgroups still read halo pixels of dz: where the two views interleave (one
+  // gradient buffer), the slot's 16 columns must lie beyond gin's C columns of the same rows
+  const char *xp = (const char*)x.data_ptr(), *zp = (const char*)dz.data_ptr(), *gp = (const char*)gin.data_ptr();
+  if (zp < gp + gb && gp < zp + zb) {
+    const int64_t col = zp >= gp ? ((zp - gp) / e) % ldg : -1;
+    TORCH_CHECK(ldz == ldg && col >= C && col + 16 <= ldg,
+                "hcb.dense_conv3x3_dgrad: dz and gin overlap: one buffer, the slot at or beyond C_in");
+  }
+  TORCH_CHECK(!(xp < gp + gb && gp < xp + xb), "hcb.dense_conv3x3_dgrad: x and gin overlap");
+  check_f32(w, "w");
+  TORCH_CHECK(w.is_contiguous() && w.dim() >= 2 && w.size(0) >= Nout && w.numel() == w.size(0) * 9 * C,
+              "hcb.dense_conv3x3_dgrad: w must be the contiguous float32 kernel [>= Nout][3][3][C_in]");
+  check_cuda(ws, "ws");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= pl.ws_floats,
+              "hcb.dense_conv3x3_dgrad: the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ",
+              pl.ws_floats, " (dense_conv3x3_dgrad_ws)");
+  check_f32(dgamma, "dgamma");
+  check_f32(dbeta, "dbeta");
+  TORCH_CHECK(dgamma.is_contiguous() && dbeta.is_contiguous() && dgamma.numel() >= C && dbeta.numel() >= C,
+              "hcb.dense_conv3x3_dgrad: dgamma / dbeta must be contiguous float32 [>= C_in]");
+  hcb::DenseDgradParams p{};
+  p.x = x.data_ptr();
+  p.dz = dz.data_ptr();
+  p.gin = gin.data_ptr();
+  p.w = w.data_ptr<float>();
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.mean = opt_f32(mean, C, "saved_mean");
+  p.invstd = opt_f32(invstd, C, "saved_invstd");
+  p.ws = ws.data_ptr<float>();
+  p.dgamma = dgamma.data_ptr<float>();
+  p.dbeta = dbeta.data_ptr<float>();
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldz = (int)ldz; p.ldg = (int)ldg;
+  p.Nout = (int)Nout; p.ldw = (int)(9 * C);
+  p.dz_bytes = (uint32_t)zb;
+  hcb::launch_dense_conv3x3_dgrad(p, cur_stream(), f32);
+}
+
 static int pack_mode(const Tensor& t, const char* what) {
   switch (t.scalar_type()) {
     case at::kFloat: return 0;
@@ -1975,6 +2061,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("dense_conv3x3_wgrad(Tensor x, Tensor dz, Tensor gamma, Tensor beta, Tensor saved_mean, Tensor saved_invstd, "
         "Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
   m.def("dense_conv3x3_wgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_wgrad_ws);
+  m.def("dense_conv3x3_dgrad(Tensor x, Tensor dz, Tensor(a!) gin, Tensor w, Tensor gamma, Tensor beta, Tensor saved_mean, "
+        "Tensor saved_invstd, Tensor(b!) ws, Tensor(c!) dgamma, Tensor(d!) dbeta, int[] geom) -> ()");
+  m.def("dense_conv3x3_dgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_dgrad_ws);
   m.def("bn_relu_maxpool_acc(Tensor z, Tensor(a!) y, Tensor(b!) amax, int[] geom, Tensor acc, int R, float eps, "
         "float momentum, Tensor gamma, Tensor beta, Tensor(c!) saved_mean, Tensor(d!) saved_invstd, "
         "Tensor(e!) run_mean, Tensor(f!) run_var, Tensor? shift=None) -> ()");
@@ -2048,6 +2137,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("lrn_bwd", lrn_bwd);
   m.impl("dense_conv3x3_fwd", dense_conv3x3_fwd);
   m.impl("dense_conv3x3_wgrad", dense_conv3x3_wgrad);
+  m.impl("dense_conv3x3_dgrad", dense_conv3x3_dgrad);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);
   m.impl("bucket_unpack", bucket_unpack);

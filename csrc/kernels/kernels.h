@@ -332,6 +332,35 @@ struct DenseWgradPlan {
 bool dense_conv3x3_wgrad_plan(int N, int H, int W, int C, bool f32, DenseWgradPlan* out);
 void launch_dense_conv3x3_wgrad(const DenseWgradParams& p, hipStream_t st, bool f32);
 
+// ---------------------------------------------------------------- dense layer data gradient + BN-ReLU backward (dense3x3_dgrad.hip)
+// da = conv3x3 data gradient of dz (column 0 of the layer's 16-channel slot, row stride ldz) with the fp32 master
+// kernel w [16][9 * C] (row stride ldw, rows < Nout used), masked by relu'(BN(x)), reduced to dbeta / dgamma
+// (overwritten) and applied as the BatchNorm backward ADDED into gin (channels [0, C) of the gradient buffer, row
+// stride ldg, x's type; its bytes are disjoint from dz's). da is never stored. Three launches without atomics:
+// per (32-channel chunk, pixel slab) sums into ws [nslabs][2][C rounded up to 32] (caller-owned, never zeroed,
+// every element read is written first), a fold in slab order, the apply pass.
+struct DenseDgradParams {
+  const void* x;
+  const void* dz;
+  void* gin;
+  const float* w;
+  const float *gamma, *beta, *mean, *invstd;  // [C]
+  float* ws;
+  float *dgamma, *dbeta;  // [C]
+  int N, H, W, C, ldx, ldz, ldg, Nout, ldw;
+  uint32_t dz_bytes;
+  int TR, patch_pix, strips_per_img, nstrips, strips_per_slab, nslabs;  // set by the launcher
+};
+struct DenseDgradPlan {
+  int TR, patch_pix, strips_per_img, nstrips, strips_per_slab, nslabs;
+  size_t lds_bytes;
+  int64_t ws_floats;
+};
+// strip rows, slab count and workspace floats of this problem (a function of the shape alone); false when
+// even one-row strips of this width do not fit the LDS budget
+bool dense_conv3x3_dgrad_plan(int N, int H, int W, int C, bool f32, DenseDgradPlan* out);
+void launch_dense_conv3x3_dgrad(const DenseDgradParams& p, hipStream_t st, bool f32);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

@@ -17,7 +17,13 @@ Fn.dense_conv3x3_wgrad: two launches, partials + fold) against bn_apply_acc re-m
 conv_wgrad reading it back, by the same method (the unfused chain is again not charged its accumulator copy,
 nor the fp32 path's split of dz, which the data gradient needs either way).
 
-    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all] [--wgrad]
+--dgrad times the data gradient with the ReLU and BatchNorm backward of the same layers: the fused op
+(csrc/kernels/dense3x3_dgrad.hip, Fn.dense_conv3x3_dgrad: three launches, reduce + fold + apply) against
+conv_dgrad writing the operand's gradient and bn_backward_acc (bn_bwd_reduce_acc + bn_bwd_apply_acc) reading it
+back, by the same method. The unfused chain is charged the fp32 path's split of dz (to_planes: with the fused
+weight gradient nothing else needs it); it is not charged the per-step zeroing of its statistics accumulator.
+
+    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all] [--wgrad | --dgrad]
 """
 import argparse
 import os
@@ -27,7 +33,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from azure_hc_intel_tf_amd.nn.layers import empty_op, set_gpu_compute_dtype  # noqa: E402
+from azure_hc_intel_tf_amd.nn.layers import empty_act, empty_op, set_gpu_compute_dtype  # noqa: E402
 from azure_hc_intel_tf_amd.nn.params import ParamStore  # noqa: E402
 from azure_hc_intel_tf_amd.ops import functional as Fn  # noqa: E402
 from azure_hc_intel_tf_amd.ops.functional import ConvSpec  # noqa: E402
@@ -107,6 +113,71 @@ def wgrad_main(args):
     set_gpu_compute_dtype(torch.bfloat16)
 
 
+def dgrad_main(args):
+    N = args.batch
+    print(f"# data gradient + BN-ReLU backward: batch {N}, {args.iters} launches per round, median of {args.rounds} "
+          "rounds, random data, warm cache")
+    print("# dtype  H  C_in | fused us  fused(A/A) us | split us + dgrad us + bn bwd us = unfused us | unfused / fused | fused GB/s")
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        set_gpu_compute_dtype(dt)
+        Fn.set_f32_native(name == "fp32")
+        e = 4 if name == "fp32" else 2
+        for H, C in layer_shapes(12, args.all):
+            M = N * H * H
+            buf = torch.randn(N, H, H, C + SLOT, device="cuda").to(dt)
+            G = (torch.randn(N, H, H, C + SLOT, device="cuda") * 1e-3).to(dt)
+            spec = ConvSpec(cin=C, cin_pad=C, cout=SLOT, kh=3, kw=3, pt=1, pl=1, pb=1, pr=1)
+            ps = ParamStore(seed=0)
+            p = ps.add("w", (SLOT, 3, 3, C), True, ps.trunc_normal((2.0 / 9 / K) ** 0.5))
+            pk = ps.add_pack(p, SLOT, 3, 3, C, spec.Kpad, spec.Kpad_t, want_tr=True)
+            ps.finalize("cuda", pack_lo=name == "fp32")
+            p.data[K:] = 0  # the pad rows
+            ps.repack()
+            gamma, beta = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
+            x = buf[..., :C].float().reshape(M, C)
+            mean = x.mean(0)
+            invstd = torch.rsqrt(x.var(0, unbiased=False) + EPS)
+            dg, db = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
+            acc_b = torch.zeros(R, 2, C, device="cuda")
+            da = empty_act((N, H, H, C), "cuda")
+            ws = Fn.dense_dgrad_workspace(buf.shape, C, dt, "cuda")
+            dz, gin = G[..., C:], G[..., :C]
+            dzp = [Fn.to_planes(dz) if name == "fp32" else dz]
+
+            def fused():
+                Fn.dense_conv3x3_dgrad(buf, C, dz, p.data, gamma, beta, mean, invstd, gin, dg, db, K, ws=ws)
+
+            def split():
+                if name == "fp32":
+                    dzp[0] = Fn.to_planes(dz)
+
+            def dgrad():
+                Fn.conv_dgrad(dzp[0], spec, pk.tr, p.data, da, False)
+
+            def bnb():
+                Fn.bn_backward_acc(da, None, buf[..., :C], Fn.BNSaved(mean, invstd), gamma, beta, 2, dg, db, gin, acc_b, R,
+                                   add=gin)
+
+            ops = {"fused": fused, "fused2": fused, "split": split, "conv": dgrad, "bn": bnb}
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            m = {k: statistics.median(v) for k, v in t.items()}
+            if name != "fp32":
+                m["split"] = 0.0
+            un = m["split"] + m["conv"] + m["bn"]
+            gbs = M * 4 * C * e / (m["fused"] * 1e-6) / 1e9  # algorithmic bytes: x twice, gin read and written
+            print(f"{name:5s} {H:3d} {C:5d} | {m['fused']:8.1f} {m['fused2']:8.1f} | {m['split']:6.1f} + {m['conv']:8.1f} + "
+                  f"{m['bn']:8.1f} = {un:8.1f} | {un / m['fused']:5.2f} | {gbs:6.0f}", flush=True)
+    Fn.set_f32_native(False)
+    set_gpu_compute_dtype(torch.bfloat16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -114,9 +185,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--all", action="store_true", help="every layer (default: first, middle and last of each block)")
     ap.add_argument("--wgrad", action="store_true", help="the weight gradient instead of the forward pass")
+    ap.add_argument("--dgrad", action="store_true", help="the data gradient with the BN-ReLU backward instead")
     args = ap.parse_args()
     if args.wgrad:
         return wgrad_main(args)
+    if args.dgrad:
+        return dgrad_main(args)
     N = args.batch
     print(f"# batch {N}, {args.iters} launches per round, median of {args.rounds} rounds, random data, warm cache")
     print("# dtype  H  C_in | fused us  fused(A/A) us | bn apply us + conv us = unfused us | unfused / fused | fused GB/s")
