@@ -39,7 +39,7 @@ def check_dataset(p: Params) -> str:
     CIFAR-10 trains its own ResNets, its own AlexNet (and ``trivial``) at 32 x 32 and has neither colour
     distortion nor a resize; those ResNets exist for CIFAR-10 only, while ``alexnet`` without the flag is the
     ImageNet model."""
-    from ..models import CIFAR_DENSENETS, CIFAR_MODELS, REFUSED_MODELS, dataset_model_names
+    from ..models import CIFAR_DENSENETS, CIFAR_MODELS, CIFAR_RESNETS_V2, REFUSED_MODELS, dataset_model_names
 
     if p.model in REFUSED_MODELS:
         raise ValueError(f"--model={p.model} is refused: {REFUSED_MODELS[p.model]}")
@@ -48,7 +48,7 @@ def check_dataset(p: Params) -> str:
         raise ValueError(f"--data_name={name}: the datasets are {', '.join(DATASET_EPOCH_IMAGES)}")
     if name == "cifar10":
         # (alexnet: with this dataset the name is the CIFAR-10 AlexNet, models.create_model(data_name=))
-        allowed = CIFAR_MODELS + ("trivial",) + tuple(dataset_model_names("cifar10")) + CIFAR_DENSENETS
+        allowed = CIFAR_MODELS + ("trivial",) + tuple(dataset_model_names("cifar10")) + CIFAR_DENSENETS + CIFAR_RESNETS_V2
         if p.model not in allowed:
             raise ValueError(f"--data_name=cifar10 runs the models {', '.join(allowed)}, not --model={p.model}")
         if p.color_distortions:
@@ -59,9 +59,9 @@ def check_dataset(p: Params) -> str:
             raise ValueError("--gpu_jpeg_decode decodes ImageNet JPEGs: CIFAR-10 has none (not with --data_name=cifar10)")
         if p.image_size and p.image_size != 32:
             raise ValueError("--data_name=cifar10 images are 32 x 32: --image_size must be 32 or absent")
-    elif p.model in CIFAR_MODELS + CIFAR_DENSENETS:
+    elif p.model in CIFAR_MODELS + CIFAR_DENSENETS + CIFAR_RESNETS_V2:
         raise ValueError(f"--model={p.model} is a CIFAR-10 model: it needs --data_name=cifar10 "
-                         f"(CIFAR-10 models: {', '.join(CIFAR_MODELS + CIFAR_DENSENETS)})")
+                         f"(CIFAR-10 models: {', '.join(CIFAR_MODELS + CIFAR_DENSENETS + CIFAR_RESNETS_V2)})")
     return name
 
 

@@ -47,7 +47,7 @@ FLAGS: List[Flag] = [
     Flag("num_batches", None, int, "timed steps (default 100; with --eval on real data and neither this nor "
          "--num_epochs given: one pass over the validation split)"),
     Flag("model", "trivial", str, "model name: resnet50|101|152[_v1.5], inception3, mobilenet, vgg11|16|19, alexnet, googlenet, "
-         "overfeat, lenet, trivial; with --data_name=cifar10: resnet20|32|44|56|110, densenet40_k12|densenet100_k12 "
+         "overfeat, lenet, trivial; with --data_name=cifar10: resnet20|32|44|56|110[_v2], densenet40_k12|densenet100_k12 "
          "(default batch 64; densenet100_k24 is refused: 2,320 channels against the BatchNorm kernels' 2048), trivial, "
          "alexnet (there the CIFAR-10 AlexNet: two 5x5 convs with local response normalisation, default batch 128)"),
     Flag("num_intra_threads", 0, int, "host intra-op threads (CPU path: torch.set_num_threads)"),
@@ -81,7 +81,7 @@ FLAGS: List[Flag] = [
          "python pickles (data_batch_1..5, test_batch; also looked for in its cifar-10-batches-py/); absent = "
          "synthetic images of the dataset's size"),
     Flag("data_name", None, str, "dataset: imagenet (default; 224 x 224, 1001 classes, 1,281,167 images per epoch) | "
-         "cifar10 (32 x 32, 11 classes, 50,000 images per epoch, held in device memory; models resnet20|32|44|56|110, "
+         "cifar10 (32 x 32, 11 classes, 50,000 images per epoch, held in device memory; models resnet20|32|44|56|110[_v2], "
          "densenet40_k12|densenet100_k12, trivial, alexnet)"),
     Flag("datasets_num_private_threads", None, int, "TFRecord reader threads per worker (real data)"),
     Flag("num_decode_threads", None, int, "JPEG decode threads per worker (real data)"),
@@ -217,7 +217,8 @@ def noop_flags_set(p: Params) -> Dict[str, Any]:
 # for the launcher's config echo; tests/test_cli.py checks it against the model classes.
 FP32_NATIVE_MODELS = frozenset({"resnet50", "resnet50_v1.5", "resnet101", "resnet101_v1.5", "resnet152",
                                 "resnet152_v1.5", "resnet50_v2", "resnet101_v2", "resnet152_v2", "resnet20", "resnet32", "resnet44",
-                                "resnet56", "resnet110", "densenet40_k12", "densenet100_k12", "inception3", "mobilenet", "vgg11", "vgg16", "vgg19", "alexnet", "overfeat",
+                                "resnet56", "resnet110", "resnet20_v2", "resnet32_v2", "resnet44_v2", "resnet56_v2", "resnet110_v2",
+                                "densenet40_k12", "densenet100_k12", "inception3", "mobilenet", "vgg11", "vgg16", "vgg19", "alexnet", "overfeat",
                                 "lenet", "googlenet", "trivial"})
 
 

@@ -28,10 +28,21 @@ def _resnet_cifar(depth):
     return make
 
 
+def _resnet_cifar_v2(depth):
+    def make(**kw):
+        from .resnet_cifar import ResNetCifarV2
+
+        return ResNetCifarV2(depth=depth, **kw)
+
+    return make
+
+
 # the CIFAR-10 ResNets (32 x 32 input): built only with --data_name=cifar10
 CIFAR_MODELS = ("resnet20", "resnet32", "resnet44", "resnet56", "resnet110")
 # the CIFAR-10 DenseNets (growth rate 12), under the same rule: a tuple of their own beside the ResNets'
 CIFAR_DENSENETS = ("densenet40_k12", "densenet100_k12")
+# the CIFAR-10 pre-activation ResNets, under the same rule (CIFAR_MODELS itself stays the five v1 names)
+CIFAR_RESNETS_V2 = tuple(f"{n}_v2" for n in CIFAR_MODELS)
 # upstream names this project refuses, with the reason
 REFUSED_MODELS = {
     "densenet100_k24": "its third dense block reaches 2,320 channels and the BatchNorm kernels stop at C <= 2048",
@@ -40,7 +51,7 @@ REFUSED_MODELS = {
 
 def cifar_only_models():
     """Every model that exists for --data_name=cifar10 only."""
-    return CIFAR_MODELS + CIFAR_DENSENETS
+    return CIFAR_MODELS + CIFAR_DENSENETS + CIFAR_RESNETS_V2
 
 
 def _densenet_cifar(depth):
@@ -90,6 +101,7 @@ _MODELS = {
     "resnet101_v2": _resnet_v2(101),
     "resnet152_v2": _resnet_v2(152),
     **{name: _resnet_cifar(int(name[len("resnet"):])) for name in CIFAR_MODELS},
+    **{name: _resnet_cifar_v2(int(name[len("resnet"):-len("_v2")])) for name in CIFAR_RESNETS_V2},
     "densenet40_k12": _densenet_cifar(40),
     "densenet100_k12": _densenet_cifar(100),
     "inception3": _inception3,

@@ -32,7 +32,7 @@ accumulate mode in the shortcut kernel, no unfused BN reduction.
 """
 from __future__ import annotations
 
-from ..nn.layers import ConvBN, GlobalAvgPool, Logits, PadShortcut
+from ..nn.layers import BNReLU, ConvBN, GlobalAvgPool, Logits, PadShortcut, PreActConv, empty_act
 from .base import CNNModel
 
 LAYER_COUNTS = {20: (3, 3, 3), 32: (5, 5, 5), 44: (7, 7, 7), 56: (9, 9, 9), 110: (18, 18, 18)}
@@ -147,3 +147,110 @@ class ResNetCifar(CNNModel):
             units.append((lambda d, b=self.blocks[i], p=prev: b.backward(d, p), self.blocks[i].layers()))
         units.append((self._stem_backward, [self.stem]))
         yield from self._segments_from_units(dx, [self.fc, self.gap], units)
+
+
+class PreActBasicBlock:
+    """The v2 basic block: a = relu(bn(x)); conv 3x3 (stride) on a + BN + ReLU (``nn.layers.PreActConv``: one
+    fused launch with FUSE_PREACT) -> conv 3x3 without BN, bias or activation, whose GEMM epilogue adds the
+    shortcut; no ReLU after the add. The shortcut is taken from x, not from a: the identity, or plan A
+    (``PadShortcut``). Backward: conv1's BN-backward reduction runs in the epilogue of conv2's data gradient;
+    the shortcut's gradient (dy itself, or plan A's dx) is added in the pre-activation BN's backward apply."""
+
+    def __init__(self, ps, name, in_shape, depth: int, stride: int, scratch: dict):
+        C = in_shape[2]
+        self.pc = PreActConv(ps, name, in_shape, depth, stride, scratch)
+        self.pre, self.c1 = self.pc.pre, self.pc.conv
+        self.c2 = ConvBN(ps, f"{name}/conv2", self.c1.out_shape, depth, 3, 3, 1, 1, "SAME", relu=False, bn=False,
+                         bias=False)
+        if C != depth:
+            self.sc = PadShortcut(f"{name}/shortcut", in_shape, depth, stride)
+            assert self.sc.out_shape == self.c2.out_shape
+        else:
+            assert stride == 1, "identity shortcut with stride is not used by these ResNets"
+            self.sc = None
+        self.in_shape = in_shape
+        self.out_shape = self.c2.out_shape
+
+    def layers(self):
+        return [self.pre, self.c1, self.c2]
+
+    def forward(self, x):
+        sc = self.sc.forward(x) if self.sc is not None else x
+        return self.c2.forward(self.pc.forward(x), residual=sc)
+
+    def backward(self, dy):
+        d1, gres = self.c2.backward(dy, want_gres=True, dx_bn=self.c1)  # gres = dy: the shortcut's gradient
+        return self.pc.backward(d1, self.sc.backward(gres) if self.sc is not None else gres)
+
+
+class ResNetCifarV2(CNNModel):
+    """CIFAR-10 pre-activation ResNets ``--model=resnet20_v2 | 32 | 44 | 56 | 110 --data_name=cifar10`` (upstream
+    ``ResnetCifar10Model`` with the v2 ``residual_block``; from memory, not pinned against the upstream source):
+
+      conv 3x3 (16) + BN + ReLU (the v2 stem keeps the ReLU that v1 drops)
+      -> three stages of n ``PreActBasicBlock`` at 16 / 32 / 64 channels, stride 2 on the first block of stages
+         2 and 3
+      -> BN + ReLU -> spatial mean -> affine -> classes.
+    ResNet-20 v2 has 269,754 trainable parameters at 10 classes (convs 267,696, BN 1,408, logits 650): v1's
+    count with the 32 parameters of one more BN over 16 channels. Learning rate, default batch and BN constants are
+    ``ResNetCifar``'s. Block inputs are plain tensors (16-bit or fp32, never Planes): they feed a BatchNorm
+    and a shortcut, not a GEMM."""
+
+    default_image_size = 32
+    default_batch_size = 128
+    F32_NATIVE_OK = True
+
+    def __init__(self, depth: int = 20, layer_counts=None, num_classes: int = 11, **kw):
+        self.depth = depth
+        self.layer_counts = tuple(layer_counts) if layer_counts is not None else LAYER_COUNTS[depth]
+        assert len(self.layer_counts) == len(STAGE_CHANNELS)
+        self.name = f"resnet{depth}_v2"
+        self._scratch = {}  # the re-materialised conv1 operands of the fused blocks' backward, one per shape
+        super().__init__(num_classes=num_classes, **kw)
+
+    @staticmethod
+    def lr_schedule(global_batch: int):
+        return cifar_lr_schedule(global_batch)
+
+    def build(self):
+        ps = self.ps
+        S = self.image_size
+        self.stem = ConvBN(ps, "conv0", (S, S, self.image_channels), STAGE_CHANNELS[0], 3, 3, 1, 1, "SAME",
+                           relu=True, need_dx=False, logical_cin=3)
+        shape = self.stem.out_shape
+        self.blocks = []
+        for si, (n, depth) in enumerate(zip(self.layer_counts, STAGE_CHANNELS)):
+            for bi in range(n):
+                stride = 2 if (si > 0 and bi == 0) else 1
+                blk = PreActBasicBlock(ps, f"stage{si + 1}/block{bi + 1}", shape, depth, stride, self._scratch)
+                self.blocks.append(blk)
+                shape = blk.out_shape
+        self.post = BNReLU(ps, "postnorm", shape)
+        self.gap = GlobalAvgPool("spatial_mean", shape)
+        self.fc = Logits(ps, "logits", shape[2], self.num_classes)
+        self.layers = [self.stem] + [l for b in self.blocks for l in b.layers()] + [self.post, self.gap, self.fc]
+
+    def forward(self, images):
+        x = self.stem.forward(images, out=empty_act((images.shape[0],) + tuple(self.stem.out_shape), images.device))
+        for b in self.blocks:
+            x = b.forward(x)
+        return self.fc.forward(self.gap.forward(self.post.forward(x)))
+
+    def backward(self, dlogits):
+        for _ in self.backward_segments(dlogits):
+            pass
+
+    def _stem_backward(self, dx):
+        self.stem.backward(dx)
+        return None
+
+    def backward_segments(self, dlogits):
+        dx = self.post.backward(self.gap.backward(self.fc.backward(dlogits)))
+        units = [(b.backward, b.layers()) for b in reversed(self.blocks)]
+        units.append((self._stem_backward, [self.stem]))
+        yield from self._segments_from_units(dx, [self.fc, self.gap, self.post], units)
+        self._scratch.clear()
+
+    def clear(self):
+        super().clear()
+        self._scratch.clear()

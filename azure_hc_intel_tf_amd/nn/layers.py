@@ -1276,3 +1276,79 @@ class DenseBlock(Layer):
 
     def clear(self):
         self._buf = self._st = self._ref = None
+
+
+# ------------------------------------------------------------------------------ CIFAR ResNet-v2
+# The pre-activation conv of a v2 basic block -- conv3x3(stride)(relu(bn(x))) -- in one launch (csrc/kernels/
+# preact3x3.hip, Fn.preact_conv3x3_forward) that also leaves the statistics of conv1's BatchNorm. False
+# (``HCB_FUSE_PREACT=0``): BNReLU.forward writes the operand and ConvBN.forward's GEMM reads it back, existing
+# kernels only -- the A/B partner. Default ON: resnet56_v2 at batch 128 trains 2.8 % faster in fp32 and in bf16
+# (A/A 0.04 % / 0.2 %) and runs --forward_only 11 % faster in fp32. The 16-bit --forward_only step is 15 % SLOWER
+# fused (the unfused conv1 is one GEMM with the BN in its epilogue), so it keeps the unfused chain whatever the
+# switch says (profiles/resnet_cifar_v2.txt).
+FUSE_PREACT = _env_on("HCB_FUSE_PREACT")
+
+
+class PreActConv:
+    """``pre`` (the pre-activation BNReLU of the block input) and ``conv`` (conv1: 3x3 / stride + BN + ReLU) of a
+    pre-activation basic block, run as one unit. With FUSE_PREACT, on native tensors of the kernel's shapes:
+    training -- bn_stats_acc on x, then the fused op writes conv1's raw output and its statistics, and conv1's
+    own BN + ReLU apply runs as in ConvBN; the backward re-materialises the operand with bn_apply_acc into
+    ``scratch`` (a dict the model shares between its blocks and empties after each backward: one tensor per
+    stage shape) and then runs conv1's and the pre-activation's existing backward kernels. Forward-only, fp32: the
+    fused op from the moving statistics, no re-materialisation. Otherwise ``pre.forward`` then ``conv.forward``."""
+
+    def __init__(self, ps: ParamStore, name: str, in_shape, cout: int, stride: int, scratch: dict):
+        self.pre = BNReLU(ps, f"{name}/preact", in_shape)
+        self.conv = ConvBN(ps, f"{name}/conv1", in_shape, cout, 3, 3, stride, stride, "SAME")
+        self.stride, self.scratch = stride, scratch
+        self.out_shape = self.conv.out_shape
+        self._fused = False
+
+    def _fusable(self, x) -> bool:
+        if not self.conv.training and x.dtype != torch.float32:
+            return False  # (measured slower than bn_inference + conv_bn_inference: see FUSE_PREACT)
+        return (FUSE_PREACT and Fn.native(x) and not Fn.is_planes(x) and x.shape[3] in Fn.PREACT_CHANNELS
+                and self.out_shape[2] in Fn.PREACT_CHANNELS)
+
+    def forward(self, x):
+        pre, conv = self.pre, self.conv
+        self._fused = self._fusable(x)
+        if not self._fused:
+            return conv.forward(pre.forward(x))
+        N, dev = x.shape[0], x.device
+        z = empty_act((N,) + tuple(self.out_shape), dev)
+        if not conv.training:
+            Fn.preact_conv3x3_forward(x, conv.w.data, pre.gamma.data, pre.beta.data, pre.eps, z, self.stride,
+                                      running_mean=pre.rmean.data, running_var=pre.rvar.data, wpack=conv.pack.pack)
+            return conv._bn_inference(z, empty_op(tuple(z.shape), dev))
+        acc_x, _, Rx = pre._stat_bufs(N, dev)
+        acc_z, _, Rz = conv._stat_bufs(N, dev)
+        Fn.bn_stats_acc(x, acc_x, Rx, pre._shift())
+        saved_x = Fn.preact_conv3x3_forward(x, conv.w.data, pre.gamma.data, pre.beta.data, pre.eps, z, self.stride,
+                                            acc=acc_x, R=Rx, shift=pre._shift(), out_stats=acc_z, out_stats_R=Rz,
+                                            out_stats_shift=conv._shift(), momentum=pre.decay,
+                                            running_mean=pre.rmean.data, running_var=pre.rvar.data,
+                                            saved_mean=pre.sv_mean.data, saved_invstd=pre.sv_invstd.data,
+                                            wpack=conv.pack.pack)
+        y = empty_op(tuple(z.shape), dev)
+        conv._saved = (None, z, y, conv._bn_forward_acc(z, y), False)  # (the operand: re-materialised in backward)
+        pre._saved = (x, None, saved_x)
+        return y
+
+    def backward(self, d1, add):
+        """``d1``: conv1's output gradient (gated and pre-reduced when conv2's data gradient fused conv1's BN
+        backward); ``add``: the shortcut's gradient in x's layout, summed in the pre-activation BN's apply."""
+        pre, conv = self.pre, self.conv
+        if self._fused:
+            x, _, saved_x = pre._saved
+            key = (tuple(x.shape), Fn.planes_mode())
+            op = self.scratch.get(key)
+            if op is None:
+                op = self.scratch[key] = empty_op(tuple(x.shape), x.device)
+            acc_x, _, Rx = pre._acc
+            Fn.bn_forward_acc(x, pre.gamma.data, pre.beta.data, None, None, 1.0, pre.eps, op, True, acc_x, Rx,
+                              saved_x.mean, saved_x.invstd, shift=pre._shift())
+            conv._saved = (op,) + tuple(conv._saved[1:])
+        da, _ = conv.backward(d1)
+        return pre.backward(da, add=add)

@@ -1625,6 +1625,90 @@ def dense_conv3x3_forward(buf, c_in: int, slot: int, w, gamma, beta, eps: float,
     return buf
 
 
+# ------------------------------------------------- CIFAR ResNet-v2 pre-activation conv (BN-ReLU-conv3x3, stride 1 | 2)
+PREACT_CHANNELS = (16, 32, 64)
+
+
+def preact_conv3x3_forward(x, w, gamma, beta, eps: float, out, stride: int = 1, acc=None, R: int = 1, shift=None,
+                           out_stats=None, out_stats_R: int = 0, out_stats_shift=None, momentum: float = 1.0,
+                           running_mean=None, running_var=None, saved_mean=None, saved_invstd=None, wpack=None,
+                           wpack_lo=None):
+    """The first conv of a pre-activation basic block on the block's raw input ``x`` [N, H, W, ld >= c_in]:
+
+        out[..., :nout] = conv3x3_SAME(stride)(relu(gamma * (x - mean) * invstd + beta))
+
+    ``out`` [N, ceil(H / stride), ceil(W / stride), ld >= nout] is a tensor of its own (it must not overlap
+    ``x``) of x's dtype; channels past nout of its rows are left alone. ``w``: the fp32 kernel
+    [nout, 3, 3, c_in], no bias; c_in and nout are 16, 32 or 64, stride 1 or 2. 'SAME' is TensorFlow's
+    (``same_pads``: on even sizes stride 2 pads only the bottom and the right) and pads the NORMALISED map.
+    Training (``acc`` given): mean / invstd are the batch moments of x, finalised from ``acc`` -- R replicas of
+    [2][>= c_in] holding sum(x - shift), sum((x - shift)^2), as bn_stats_acc leaves them -- written to
+    ``saved_mean`` / ``saved_invstd`` (allocated when not given) and returned as BNSaved; the moving statistics
+    are updated with ``momentum`` (the decay) when given. Inference (``acc`` None): mean / variance are
+    ``running_mean`` / ``running_var``; returns None. ``out_stats`` ([>= out_stats_R][2][>= nout], another
+    tensor than ``acc``) receives sum(out - out_stats_shift), sum((out - out_stats_shift)^2) of the fp32
+    results per channel: what the BatchNorm after this conv needs, without a pass of its own.
+
+    GPU (csrc/kernels/preact3x3.hip): ONE launch; the normalised operand is never written. 16-bit tensors take
+    the 16-bit pack ``wpack`` ([nout][Kpad], K = (tap, c): a ConvBN's pack); a plain fp32 ``x`` (not Planes) is
+    normalised in fp32, split into bf16 hi / mid / lo on its way into LDS and multiplied bf16x6 with the plane
+    pack. Without ``wpack`` the operands are packed from ``w`` here (dense_pack: tools and tests).
+    CPU / non-native tensors: the formula above in PyTorch at ``x``'s dtype, which is the definition."""
+    N, H, W, _ = x.shape
+    nout, c_in = w.shape[0], w.shape[3]
+    M = N * H * W
+    (pt, pb), (pl, pr) = same_pads(H, 3, stride), same_pads(W, 3, stride)
+    P, Q = (H + stride - 1) // stride, (W + stride - 1) // stride
+    assert tuple(w.shape[1:3]) == (3, 3) and x.shape[3] >= c_in, "preact_conv3x3_forward: w is [nout, 3, 3, c_in <= x's channels]"
+    assert tuple(out.shape[:3]) == (N, P, Q) and out.shape[3] >= nout, "preact_conv3x3_forward: out is [N, P, Q, >= nout]"
+    assert acc is not None or (running_mean is not None and running_var is not None), "inference needs moving statistics"
+    train = acc is not None
+    if train and saved_mean is None:
+        saved_mean = torch.empty(c_in, dtype=torch.float32, device=x.device)
+        saved_invstd = torch.empty(c_in, dtype=torch.float32, device=x.device)
+    if native(x):
+        assert not is_planes(x) and not is_planes(out), "the pre-activation kernel reads and writes plain tensors"
+        if wpack is None:
+            wpack, wpack_lo = dense_pack(w, x.dtype)
+        elif wpack_lo is None:
+            wpack_lo = lo_pack(wpack)
+        if not train:
+            # moving statistics as one replica of shifted sums (bn_inference's form): shift = the moving
+            # mean, sum 0, sum of squares M * moving variance; nothing is updated
+            acc = torch.stack([torch.zeros_like(running_var), running_var * float(M)]).unsqueeze(0).contiguous()
+            R, shift, running_mean, running_var, momentum = 1, running_mean, None, None, 1.0
+        _ext.ops().preact_conv3x3_fwd(x, wpack, wpack_lo, out, [N, H, W, c_in, ld(x), ld(out), nout,
+                                                                _round_up(9 * c_in, 64), int(stride)],
+                                      acc, int(R), float(eps), float(momentum), gamma, beta, shift, saved_mean,
+                                      saved_invstd, running_mean, running_var, out_stats, int(out_stats_R),
+                                      out_stats_shift)
+        return BNSaved(saved_mean, saved_invstd) if train else None
+    dt = x.dtype
+    xc = x[..., :c_in]
+    if train:
+        sums = acc[:R].sum(0)[:, :c_in]
+        d = sums[0] / M
+        mean = d + (shift[:c_in] if shift is not None else 0)
+        var = (sums[1] / M - d * d).clamp(min=0)
+        invstd = torch.rsqrt(var + eps)
+        saved_mean[:c_in] = mean
+        saved_invstd[:c_in] = invstd
+        if running_mean is not None:
+            running_mean[:c_in].mul_(momentum).add_((1 - momentum) * mean)
+            running_var[:c_in].mul_(momentum).add_((1 - momentum) * var * M / max(M - 1, 1))
+    else:
+        mean, invstd = running_mean[:c_in], torch.rsqrt(running_var[:c_in] + eps)
+    a = torch.relu((xc - mean.to(dt)) * (invstd * gamma[:c_in]).to(dt) + beta[:c_in].to(dt))
+    a = F.pad(a.permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    y = F.conv2d(a, w.to(dt).permute(0, 3, 1, 2), stride=stride).permute(0, 2, 3, 1)
+    out[..., :nout] = y
+    if out_stats is not None:
+        dy = y.reshape(-1, nout).to(out_stats.dtype) - (out_stats_shift[:nout] if out_stats_shift is not None else 0)
+        out_stats[0, 0, :nout] += dy.sum(0)
+        out_stats[0, 1, :nout] += (dy * dy).sum(0)
+    return BNSaved(saved_mean, saved_invstd) if train else None
+
+
 def dense_wgrad_workspace(shape, c_in, dtype, device):
     """The caller-owned workspace of dense_conv3x3_wgrad for a buffer of ``shape`` [N, H, W, ld] read up to
     ``c_in`` channels: [slabs * 16 * 9 * round_up(c_in, 32)] fp32, never zeroed. The slab count depends on

@@ -1594,6 +1594,98 @@ void dense_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Ten
   hcb::launch_dense_conv3x3(p, cur_stream(), f32);
 }
 
+// ---- ResNet-v2 (CIFAR) pre-activation conv (preact3x3.hip): y = conv3x3_SAME(stride)(relu(BN(x))) in one pass.
+// geom = [N, H, W, C, ldx, ldy, Nout, Kpad, stride]: x the raw NHWC block input, y a separate NHWC tensor of
+// ceil(H / stride) x ceil(W / stride) pixels and x's type; w the [Nout][Kpad] pack (16-bit; fp32: the bf16 hi
+// pack with w_lo = [2][n] mid / lo packs); acc the R replicas of [2][acc_C] holding x's statistics; stats: the
+// replicas of [2][stats_C] that receive y's statistics at columns 0 .. Nout
+void preact_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& w_lo, const Tensor& y,
+                        at::IntArrayRef g, const Tensor& acc, int64_t R, double eps, double momentum,
+                        const Tensor& gamma, const Tensor& beta, const c10::optional<Tensor>& shift,
+                        const c10::optional<Tensor>& saved_mean, const c10::optional<Tensor>& saved_invstd,
+                        const c10::optional<Tensor>& run_mean, const c10::optional<Tensor>& run_var,
+                        const c10::optional<Tensor>& stats, int64_t stats_R, const c10::optional<Tensor>& stats_shift) {
+  TORCH_CHECK(g.size() == 9, "hcb.preact_conv3x3_fwd: geom = [N, H, W, C, ldx, ldy, Nout, Kpad, stride]");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], ldy = g[5], Nout = g[6], Kpad = g[7], s = g[8];
+  const bool f32 = check_act_or_f32(x, "x");
+  check_cuda(y, "y");
+  TORCH_CHECK(x.scalar_type() == y.scalar_type(), "hcb.preact_conv3x3_fwd: y's dtype differs from x's");
+  check_act(w, "w");
+  const int64_t e = f32 ? 4 : 2;
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.preact_conv3x3_fwd: empty tensor");
+  TORCH_CHECK(C == 16 || C == 32 || C == 64, "hcb.preact_conv3x3_fwd: C_in must be 16, 32 or 64, got ", C);
+  TORCH_CHECK(Nout == 16 || Nout == 32 || Nout == 64, "hcb.preact_conv3x3_fwd: Nout must be 16, 32 or 64, got ", Nout);
+  TORCH_CHECK(s == 1 || s == 2, "hcb.preact_conv3x3_fwd: stride must be 1 or 2, got ", s);
+  TORCH_CHECK(ldx % 8 == 0 && ldy % 8 == 0, "hcb.preact_conv3x3_fwd: ld must be a multiple of 8, got ", ldx, " / ", ldy);
+  TORCH_CHECK(ldx >= C && ldy >= Nout, "hcb.preact_conv3x3_fwd: rows of ", ldx, " / ", ldy, " channels do not hold C_in = ", C,
+              " / Nout = ", Nout);
+  TORCH_CHECK(x.stride(-1) == 1 && y.stride(-1) == 1, "hcb.preact_conv3x3_fwd: non-contiguous rows (channel stride must be 1)");
+  TORCH_CHECK(Kpad % 8 == 0 && Kpad >= 9 * C, "hcb.preact_conv3x3_fwd: Kpad must be a multiple of 8 >= 9 * C_in");
+  TORCH_CHECK(hcb::preact_conv3x3_fits((int)N, (int)H, (int)W, (int)C, (int)Nout, (int)s, f32),
+              "hcb.preact_conv3x3_fwd: W = ", W, " with Nout = ", Nout, " is larger than the strip and patch the LDS budget allows");
+  const int64_t P = (H + s - 1) / s, Q = (W + s - 1) / s;
+  const int64_t xb = ((N * H * W - 1) * ldx + C) * e, yb = ((N * P * Q - 1) * ldy + Nout) * e, wb = Nout * Kpad * 2;
+  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31) && wb < (1ll << 31),
+              "hcb.preact_conv3x3_fwd: tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(y, yb, "y");
+  check_range(w, wb, "w");
+  check_align16(x.data_ptr(), "x");
+  check_align16(y.data_ptr(), "y");
+  check_align16(w.data_ptr(), "w");
+  const char *xp = (const char*)x.data_ptr(), *yp = (const char*)y.data_ptr();
+  TORCH_CHECK(!(xp < yp + yb && yp < xp + xb), "hcb.preact_conv3x3_fwd: y aliases x (other workgroups still read the halo)");
+  hcb::PreactParams p{};
+  p.x = x.data_ptr();
+  p.y = y.data_ptr();
+  p.w = w.data_ptr();
+  if (f32) {
+    TORCH_CHECK(w_lo.has_value() && w_lo->dim() == 2 && w_lo->size(0) == 2 && w_lo->stride(1) == 1 &&
+                    w_lo->scalar_type() == w.scalar_type() && w_lo->size(1) >= Nout * Kpad,
+                "hcb.preact_conv3x3_fwd: fp32 needs w_lo = [2][>= Nout*Kpad] of the pack's type");
+    check_cuda(*w_lo, "w_lo");
+    const Tensor m = w_lo->select(0, 0), l = w_lo->select(0, 1);
+    check_align16(m.data_ptr(), "w_lo[0]");
+    check_align16(l.data_ptr(), "w_lo[1]");
+    p.w_mid = m.data_ptr();
+    p.w_lo = l.data_ptr();
+  }
+  check_f32(acc, "acc");
+  TORCH_CHECK(R >= 1 && acc.dim() == 3 && acc.is_contiguous() && acc.size(0) >= R && acc.size(1) == 2 && acc.size(2) >= C,
+              "hcb.preact_conv3x3_fwd: acc must be contiguous [>= R][2][>= C_in]");
+  p.acc = acc.data_ptr<float>();
+  p.R = (int)R;
+  p.acc_C = (int)acc.size(2);
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.shift = opt_f32(shift, C, "shift");
+  p.eps = (float)eps;
+  p.momentum = (float)momentum;
+  p.saved_mean = const_cast<float*>(opt_f32(saved_mean, C, "saved_mean"));
+  p.saved_invstd = const_cast<float*>(opt_f32(saved_invstd, C, "saved_invstd"));
+  TORCH_CHECK(run_mean.has_value() == run_var.has_value(), "hcb.preact_conv3x3_fwd: moving mean and variance come together");
+  p.run_mean = const_cast<float*>(opt_f32(run_mean, C, "run_mean"));
+  p.run_var = const_cast<float*>(opt_f32(run_var, C, "run_var"));
+  if (stats.has_value()) {
+    check_f32(*stats, "stats");
+    TORCH_CHECK(stats_R >= 1 && stats->dim() == 3 && stats->is_contiguous() && stats->size(0) >= stats_R &&
+                    stats->size(1) == 2 && stats->size(2) >= Nout,
+                "hcb.preact_conv3x3_fwd: stats must be contiguous [>= stats_R][2][>= Nout]");
+    TORCH_CHECK(stats->data_ptr() != acc.data_ptr(), "hcb.preact_conv3x3_fwd: stats and acc must be different accumulators");
+    p.stats = stats->data_ptr<float>();
+    p.stats_R = (int)stats_R;
+    p.stats_C = (int)stats->size(2);
+    p.stats_shift = opt_f32(stats_shift, Nout, "stats_shift");
+  } else {
+    TORCH_CHECK(!stats_shift.has_value(), "hcb.preact_conv3x3_fwd: stats_shift without stats");
+  }
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldy = (int)ldy;
+  p.Nout = (int)Nout; p.Kpad = (int)Kpad; p.stride = (int)s;
+  p.x_bytes = (uint32_t)xb;
+  p.w_bytes = (uint32_t)wb;
+  hcb::launch_preact_conv3x3(p, cur_stream(), f32);
+}
+
 // ---- dense layer weight gradient (dense3x3_wgrad.hip): dw[n][tap * C + c] += sum dz[.., slot + n] *
 // relu(BN(x[.., c])) shifted by the tap. geom = [N, H, W, C, ldx, slot, ldz, Nout]: x the raw NHWC concat
 // buffer, dz the layer's 16 channels of the block's gradient buffer (a view: rows of ldz channels, the
@@ -2058,6 +2150,10 @@ HCB_TORCH_LIBRARY(hcb, m) {
         "float momentum, Tensor gamma, Tensor beta, Tensor? shift=None, Tensor(b!)? saved_mean=None, "
         "Tensor(c!)? saved_invstd=None, Tensor(d!)? run_mean=None, Tensor(e!)? run_var=None, Tensor(f!)? stats=None, "
         "int stats_R=0, int stats_off=0, Tensor? stats_shift=None) -> ()");
+  m.def("preact_conv3x3_fwd(Tensor x, Tensor w, Tensor? w_lo, Tensor(a!) y, int[] geom, Tensor acc, int R, float eps, "
+        "float momentum, Tensor gamma, Tensor beta, Tensor? shift=None, Tensor(b!)? saved_mean=None, "
+        "Tensor(c!)? saved_invstd=None, Tensor(d!)? run_mean=None, Tensor(e!)? run_var=None, Tensor(f!)? stats=None, "
+        "int stats_R=0, Tensor? stats_shift=None) -> ()");
   m.def("dense_conv3x3_wgrad(Tensor x, Tensor dz, Tensor gamma, Tensor beta, Tensor saved_mean, Tensor saved_invstd, "
         "Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
   m.def("dense_conv3x3_wgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_wgrad_ws);
@@ -2136,6 +2232,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("lrn_fwd", lrn_fwd);
   m.impl("lrn_bwd", lrn_bwd);
   m.impl("dense_conv3x3_fwd", dense_conv3x3_fwd);
+  m.impl("preact_conv3x3_fwd", preact_conv3x3_fwd);
   m.impl("dense_conv3x3_wgrad", dense_conv3x3_wgrad);
   m.impl("dense_conv3x3_dgrad", dense_conv3x3_dgrad);
   m.impl("synth_labels", synth_labels);

@@ -361,6 +361,34 @@ struct DenseDgradPlan {
 bool dense_conv3x3_dgrad_plan(int N, int H, int W, int C, bool f32, DenseDgradPlan* out);
 void launch_dense_conv3x3_dgrad(const DenseDgradParams& p, hipStream_t st, bool f32);
 
+// ---------------------------------------------------------------- ResNet-v2 (CIFAR) pre-activation conv (preact3x3.hip)
+// y = conv3x3_SAME(stride)(relu(BN(x))) in one pass: x the raw NHWC block input (row stride ldx; 16-bit or
+// fp32), BN from the statistics in `acc` (R replicas of [2][acc_C]) with gamma / beta, y a separate NHWC
+// tensor of x's type (row stride ldy) with P x Q = ceil(H / stride) x ceil(W / stride) pixels. C and Nout are
+// 16, 32 or 64; stride 1 or 2 with TF's 'SAME' pads. w: the [Nout][Kpad] pack, K = (tap, c); fp32: the bf16
+// hi pack with w_mid / w_lo beside it.
+struct PreactParams {
+  const void* x;
+  void* y;
+  const void* w;
+  const void* w_mid;
+  const void* w_lo;
+  const float* acc;
+  int R, acc_C;
+  const float *gamma, *beta, *shift;  // [C]; shift: the K of acc's sums (null = 0)
+  float eps, momentum;
+  float *saved_mean, *saved_invstd, *run_mean, *run_var;  // [C] or null: published by block (0, 0)
+  float* stats;  // null, or stats_R replicas of [2][stats_C] receiving sum(y - K), sum((y - K)^2) at columns 0 .. Nout
+  int stats_R, stats_C;
+  const float* stats_shift;  // [Nout] or null
+  int N, H, W, C, ldx, ldy, Nout, Kpad, stride;
+  uint32_t x_bytes, w_bytes;
+  int P, Q, pt, pl, TR, strips_per_img, nstrips, PW, patch_pix;  // set by the launcher
+};
+// whether the shape is one the kernel takes and a one-row strip of it fits the LDS budget
+bool preact_conv3x3_fits(int N, int H, int W, int C, int Nout, int stride, bool f32);
+void launch_preact_conv3x3(const PreactParams& p, hipStream_t st, bool f32);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

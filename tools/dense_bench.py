@@ -23,7 +23,12 @@ conv_dgrad writing the operand's gradient and bn_backward_acc (bn_bwd_reduce_acc
 back, by the same method. The unfused chain is charged the fp32 path's split of dz (to_planes: with the fused
 weight gradient nothing else needs it); it is not charged the per-step zeroing of its statistics accumulator.
 
-    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all] [--wgrad | --dgrad]
+--preact times the pre-activation conv of the CIFAR ResNet-v2 blocks instead (csrc/kernels/preact3x3.hip,
+Fn.preact_conv3x3_forward: one launch, output statistics included) against bn_apply_acc writing the operand and
+the existing conv GEMM (statistics in its epilogue) reading it back, on the five layer shapes of those models
+(default batch 128 there: pass --batch 128), by the same method. Neither side is charged bn_stats_acc.
+
+    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all] [--wgrad | --dgrad | --preact]
 """
 import argparse
 import os
@@ -178,6 +183,66 @@ def dgrad_main(args):
     set_gpu_compute_dtype(torch.bfloat16)
 
 
+# (H, C_in, Nout, stride) of the pre-activation convs of resnet20_v2 .. resnet110_v2
+PREACT_SHAPES = ((32, 16, 16, 1), (32, 16, 32, 2), (16, 32, 32, 1), (16, 32, 64, 2), (8, 64, 64, 1))
+
+
+def preact_main(args):
+    N = args.batch
+    print(f"# pre-activation conv: batch {N}, {args.iters} launches per round, median of {args.rounds} rounds, random "
+          "data, warm cache")
+    print("# dtype  H  C_in Nout s | fused us  fused(A/A) us | bn apply us + conv us = unfused us | unfused / fused | fused GB/s")
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        set_gpu_compute_dtype(dt)
+        Fn.set_f32_native(name == "fp32")
+        e = 4 if name == "fp32" else 2
+        for H, C, nout, s in PREACT_SHAPES:
+            M, P = N * H * H, H // s
+            x = torch.randn(N, H, H, C, device="cuda").to(dt)
+            pads = Fn.same_pads(H, 3, s)
+            spec = ConvSpec(cin=C, cin_pad=C, cout=nout, kh=3, kw=3, sh=s, sw=s, pt=pads[0], pl=pads[0], pb=pads[1],
+                            pr=pads[1])
+            ps = ParamStore(seed=0)
+            p = ps.add("w", (nout, 3, 3, C), True, ps.variance_scaling(9 * C))
+            pk = ps.add_pack(p, nout, 3, 3, C, spec.Kpad, spec.Kpad_t, want_tr=False)
+            ps.finalize("cuda", dtype_pack=torch.bfloat16, pack_lo=name == "fp32")
+            gamma, beta = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
+            xf = x.float().reshape(M, C)
+            acc = torch.zeros(R, 2, C, device="cuda")
+            acc[:, 0], acc[:, 1] = xf.sum(0) / R, (xf * xf).sum(0) / R
+            acc_o = torch.zeros(R, 2, nout, device="cuda")
+            sv = torch.empty(2, C, device="cuda")
+            op = empty_op((N, H, H, C), "cuda")  # the normalised operand of the unfused chain (Planes on fp32)
+            z = empty_act((N, P, P, nout), "cuda")
+
+            def fused():
+                Fn.preact_conv3x3_forward(x, p.data, gamma, beta, EPS, z, s, acc=acc, R=R, out_stats=acc_o, out_stats_R=R,
+                                          saved_mean=sv[0], saved_invstd=sv[1], wpack=pk.pack)
+
+            def bn():
+                Fn.bn_forward_acc(x, gamma, beta, None, None, 1.0, EPS, op, True, acc, R, sv[0], sv[1])
+
+            def conv():
+                Fn.conv_forward(op, spec, pk.pack, p.data, z, stats=acc_o, stats_R=R)
+
+            ops = {"fused": fused, "fused2": fused, "bn": bn, "conv": conv}
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            m = {k: statistics.median(v) for k, v in t.items()}
+            un = m["bn"] + m["conv"]
+            gbs = (M * C + N * P * P * nout) * e / (m["fused"] * 1e-6) / 1e9  # algorithmic bytes: x once, y once
+            print(f"{name:5s} {H:3d} {C:4d} {nout:4d} {s} | {m['fused']:8.1f} {m['fused2']:8.1f} | {m['bn']:8.1f} + "
+                  f"{m['conv']:8.1f} = {un:8.1f} | {un / m['fused']:5.2f} | {gbs:6.0f}", flush=True)
+    Fn.set_f32_native(False)
+    set_gpu_compute_dtype(torch.bfloat16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -186,7 +251,10 @@ def main():
     ap.add_argument("--all", action="store_true", help="every layer (default: first, middle and last of each block)")
     ap.add_argument("--wgrad", action="store_true", help="the weight gradient instead of the forward pass")
     ap.add_argument("--dgrad", action="store_true", help="the data gradient with the BN-ReLU backward instead")
+    ap.add_argument("--preact", action="store_true", help="the CIFAR ResNet-v2 pre-activation conv instead")
     args = ap.parse_args()
+    if args.preact:
+        return preact_main(args)
     if args.wgrad:
         return wgrad_main(args)
     if args.dgrad:
