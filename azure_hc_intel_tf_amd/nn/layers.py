@@ -1288,6 +1288,27 @@ class DenseBlock(Layer):
 # switch says (profiles/resnet_cifar_v2.txt).
 FUSE_PREACT = _env_on("HCB_FUSE_PREACT")
 
+# The weight gradient of that conv from the block's RAW input, BatchNorm and ReLU applied on the way into LDS
+# (csrc/kernels/preact3x3_wgrad.hip, Fn.preact_conv3x3_wgrad): the backward neither re-materialises the operand nor
+# allocates the scratch for it. Takes effect only where the forward ran fused. False: bn_forward_acc writes the
+# operand and conv_wgrad reads it back -- the A/B partner. Default OFF (``HCB_FUSE_PREACT_WGRAD=1`` turns it on): the
+# captured resnet56_v2 step at batch 128 measured 4.4 % SLOWER in fp32 and 3.6 % slower in bf16 with it (A/A 0.01 % /
+# 0.2 %): the op wins on the 32 x 32 and 16 x 16 stride-1 layers (2.0x .. 1.3x) and loses on the 64-column layers
+# (0.55x at 8 x 8 x 64 in fp32), where its slab rule leaves few workgroups (profiles/resnet_cifar_v2_wgrad.txt).
+FUSE_PREACT_WGRAD = os.environ.get("HCB_FUSE_PREACT_WGRAD", "0") == "1"
+
+
+class _PreActConv1(ConvBN):
+    """conv1 of a pre-activation block: a ConvBN whose weight gradient PreActConv.backward may redirect to the fused
+    op on the block's raw input (``pre_wgrad``, set for one backward; None = ConvBN's own)."""
+
+    pre_wgrad = None
+
+    def _wgrad(self, dz, x):
+        if self.pre_wgrad is None:
+            return super()._wgrad(dz, x)
+        self.pre_wgrad(dz, x)
+
 
 class PreActConv:
     """``pre`` (the pre-activation BNReLU of the block input) and ``conv`` (conv1: 3x3 / stride + BN + ReLU) of a
@@ -1295,12 +1316,14 @@ class PreActConv:
     training -- bn_stats_acc on x, then the fused op writes conv1's raw output and its statistics, and conv1's
     own BN + ReLU apply runs as in ConvBN; the backward re-materialises the operand with bn_apply_acc into
     ``scratch`` (a dict the model shares between its blocks and empties after each backward: one tensor per
-    stage shape) and then runs conv1's and the pre-activation's existing backward kernels. Forward-only, fp32: the
+    stage shape) and then runs conv1's and the pre-activation's existing backward kernels -- or, with
+    FUSE_PREACT_WGRAD, conv1's weight gradient reads the raw input (Fn.preact_conv3x3_wgrad; ``scratch`` then holds
+    only its workspace) and nothing is re-materialised. Forward-only, fp32: the
     fused op from the moving statistics, no re-materialisation. Otherwise ``pre.forward`` then ``conv.forward``."""
 
     def __init__(self, ps: ParamStore, name: str, in_shape, cout: int, stride: int, scratch: dict):
         self.pre = BNReLU(ps, f"{name}/preact", in_shape)
-        self.conv = ConvBN(ps, f"{name}/conv1", in_shape, cout, 3, 3, stride, stride, "SAME")
+        self.conv = _PreActConv1(ps, f"{name}/conv1", in_shape, cout, 3, 3, stride, stride, "SAME")
         self.stride, self.scratch = stride, scratch
         self.out_shape = self.conv.out_shape
         self._fused = False
@@ -1336,10 +1359,34 @@ class PreActConv:
         pre._saved = (x, None, saved_x)
         return y
 
+    def _wgrad_fused(self, dz, x):
+        """conv1's weight gradient from the raw block input ``x`` (called through run_wgrad: side-stream capable). The
+        workspace is shared by the blocks of a stage through ``scratch``: every weight gradient of a step is ordered
+        on one stream."""
+        pre, conv = self.pre, self.conv
+        nout = self.out_shape[2]
+        key = ("preact_wgrad_ws", tuple(x.shape), nout, self.stride)
+        ws = self.scratch.get(key)
+        if ws is None:
+            ws = self.scratch[key] = Fn.preact_wgrad_workspace(x.shape, x.shape[3], nout, self.stride, x.dtype, x.device)
+        if WGRAD_SIDE["stream"] is not None:
+            WGRAD_SIDE["keep"].append(ws)  # (the model empties ``scratch`` before the side stream is joined)
+        dz = Fn.from_planes(dz)  # (fp32 path: conv1's BN backward wrote the data gradient's Planes)
+        saved_x = pre._saved[2]
+        Fn.preact_conv3x3_wgrad(x, x.shape[3], dz, pre.gamma.data, pre.beta.data, saved_x.mean, saved_x.invstd,
+                                conv.w.grad.view(nout, -1), self.stride, ws=ws)
+
     def backward(self, d1, add):
         """``d1``: conv1's output gradient (gated and pre-reduced when conv2's data gradient fused conv1's BN
         backward); ``add``: the shortcut's gradient in x's layout, summed in the pre-activation BN's apply."""
         pre, conv = self.pre, self.conv
+        if self._fused and FUSE_PREACT_WGRAD:
+            x = pre._saved[0]
+            conv._saved = (x,) + tuple(conv._saved[1:])  # (the raw input: what the fused weight gradient reads)
+            conv.pre_wgrad = self._wgrad_fused
+            da, _ = conv.backward(d1)
+            conv.pre_wgrad = None
+            return pre.backward(da, add=add)
         if self._fused:
             x, _, saved_x = pre._saved
             key = (tuple(x.shape), Fn.planes_mode())

@@ -1709,6 +1709,49 @@ def preact_conv3x3_forward(x, w, gamma, beta, eps: float, out, stride: int = 1, 
     return BNSaved(saved_mean, saved_invstd) if train else None
 
 
+def preact_wgrad_workspace(shape, c_in: int, nout: int, stride: int, dtype, device):
+    """The caller-owned workspace of preact_conv3x3_wgrad for a block input of ``shape`` [N, H, W, ld]:
+    [slabs * nout * 9 * round_up(c_in, 32)] fp32, never zeroed. The slab count depends on the shape alone."""
+    N, H, W = shape[:3]
+    n = _ext.ops().preact_conv3x3_wgrad_ws([N, H, W, c_in, c_in, nout, nout, int(stride)], dtype == torch.float32)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def preact_conv3x3_wgrad(x, c_in: int, dz, gamma, beta, saved_mean, saved_invstd, dw, stride: int, ws=None):
+    """The weight gradient of a pre-activation block's first conv, with its BatchNorm and ReLU applied on the way in:
+
+        dw[n, r, t, c] += sum_{img, p, q} dz[img, p, q, n] * a[img, p * stride + r - pt, q * stride + t - pl, c]
+        a = relu(x * sc + sh),  sc = gamma * invstd,  sh = beta - mean * sc,  a = 0 outside the image
+
+    ``x`` [N, H, W, ld >= c_in]: the block's raw input; ``dz`` [N, P, Q, nout]: the gradient of conv1's raw output
+    (P = ceil(H / stride); a channel-slice view is fine; x's dtype); (pt, pl): TensorFlow's 'SAME' pads
+    (``same_pads``); ``saved_mean`` / ``saved_invstd``: the batch moments the forward saved; ``dw``: fp32
+    [nout, 9 * c_in] (conv_wgrad's layout), added into. c_in and nout are 16, 32 or 64, stride 1 or 2.
+
+    GPU (csrc/kernels/preact3x3_wgrad.hip): two launches, the normalised operand is never written; per-slab
+    partials go through ``ws`` (preact_wgrad_workspace) and are folded in slab order, so the result is bitwise
+    reproducible in every mode. 16-bit or plain fp32 tensors (not Planes). CPU / non-native tensors: the formula
+    above in PyTorch at ``x``'s dtype (torch.nn.grad.conv2d_weight on the SAME-padded normalised map), which is
+    the definition."""
+    N, H, W, _ = x.shape
+    nout = dz.shape[3]
+    (pt, pb), (pl, pr) = same_pads(H, 3, stride), same_pads(W, 3, stride)
+    if native(x):
+        assert not is_planes(x) and not is_planes(dz), "the pre-activation kernels read plain tensors"
+        if ws is None:
+            ws = preact_wgrad_workspace(x.shape, c_in, nout, stride, x.dtype, x.device)
+        _ext.ops().preact_conv3x3_wgrad(x, dz, gamma, beta, saved_mean, saved_invstd, ws, dw,
+                                        [N, H, W, c_in, ld(x), ld(dz), nout, int(stride)])
+        return dw
+    dt = x.dtype
+    sc = (saved_invstd[:c_in] * gamma[:c_in]).to(dt)
+    sh = (beta[:c_in] - saved_mean[:c_in] * saved_invstd[:c_in] * gamma[:c_in]).to(dt)
+    a = F.pad(torch.relu(x[..., :c_in] * sc + sh).permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    g = torch.nn.grad.conv2d_weight(a, (nout, c_in, 3, 3), dz.to(dt).permute(0, 3, 1, 2), stride=stride)
+    dw[:nout, :9 * c_in] += g.permute(0, 2, 3, 1).reshape(nout, 9 * c_in).to(dw.dtype)
+    return dw
+
+
 def dense_wgrad_workspace(shape, c_in, dtype, device):
     """The caller-owned workspace of dense_conv3x3_wgrad for a buffer of ``shape`` [N, H, W, ld] read up to
     ``c_in`` channels: [slabs * 16 * 9 * round_up(c_in, 32)] fp32, never zeroed. The slab count depends on

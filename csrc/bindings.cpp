@@ -1753,6 +1753,76 @@ void dense_conv3x3_wgrad(const Tensor& x, const Tensor& dz, const Tensor& gamma,
   hcb::launch_dense_conv3x3_wgrad(p, cur_stream(), f32);
 }
 
+// ---- ResNet-v2 pre-activation conv weight gradient (preact3x3_wgrad.hip): dw[n][tap * C + c] += sum dz[.., n] *
+// relu(BN(x[.., c])) at the tap's pixel. geom = [N, H, W, C, ldx, ldz, Nout, stride]: x the raw NHWC block input, dz
+// conv1's raw-output gradient [N, P, Q, >= Nout] (a channel-slice view is fine), mean / invstd the saved batch
+// statistics, ws the workspace of preact_conv3x3_wgrad_ws floats (never zeroed), dw fp32 [Nout][>= 9 * C]
+static hcb::PreactWgradPlan preact_wgrad_plan(at::IntArrayRef g, bool f32) {
+  TORCH_CHECK(g.size() == 8, "hcb.preact_conv3x3_wgrad: geom = [N, H, W, C, ldx, ldz, Nout, stride]");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], Nout = g[6], s = g[7];
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.preact_conv3x3_wgrad: empty tensor");
+  TORCH_CHECK(C == 16 || C == 32 || C == 64, "hcb.preact_conv3x3_wgrad: C_in must be 16, 32 or 64, got ", C);
+  TORCH_CHECK(Nout == 16 || Nout == 32 || Nout == 64, "hcb.preact_conv3x3_wgrad: Nout must be 16, 32 or 64, got ", Nout);
+  TORCH_CHECK(s == 1 || s == 2, "hcb.preact_conv3x3_wgrad: stride must be 1 or 2, got ", s);
+  TORCH_CHECK(N * H * W < (1ll << 31), "hcb.preact_conv3x3_wgrad: tensors must stay below 2 GiB (32-bit offsets)");
+  hcb::PreactWgradPlan pl;
+  TORCH_CHECK(W <= (1 << 20) && hcb::preact_conv3x3_wgrad_plan((int)N, (int)H, (int)W, (int)C, (int)Nout, (int)s, f32, &pl),
+              "hcb.preact_conv3x3_wgrad: W = ", W, " at stride ", s, " is wider than the strip and patch the LDS budget allows");
+  return pl;
+}
+
+int64_t preact_conv3x3_wgrad_ws(at::IntArrayRef g, bool f32) { return preact_wgrad_plan(g, f32).ws_floats; }
+
+void preact_conv3x3_wgrad(const Tensor& x, const Tensor& dz, const Tensor& gamma, const Tensor& beta, const Tensor& mean,
+                          const Tensor& invstd, const Tensor& ws, const Tensor& dw, at::IntArrayRef g) {
+  TORCH_CHECK(x.dim() == 4 && dz.dim() == 4, "hcb.preact_conv3x3_wgrad: x and dz are plain [N, H, W, C] tensors (not Planes)");
+  const bool f32 = check_act_or_f32(x, "x");
+  check_cuda(dz, "dz");
+  TORCH_CHECK(dz.scalar_type() == x.scalar_type(), "hcb.preact_conv3x3_wgrad: x and dz dtypes differ");
+  const hcb::PreactWgradPlan pl = preact_wgrad_plan(g, f32);
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], ldz = g[5], Nout = g[6];
+  const int64_t e = f32 ? 4 : 2;
+  TORCH_CHECK(ldx % 8 == 0 && ldz % 8 == 0, "hcb.preact_conv3x3_wgrad: ld must be a multiple of 8, got ", ldx, " / ", ldz);
+  TORCH_CHECK(ldx >= C && ldz >= Nout, "hcb.preact_conv3x3_wgrad: rows of ", ldx, " / ", ldz, " channels do not hold C_in = ", C,
+              " / Nout = ", Nout);
+  TORCH_CHECK(x.size(0) == N && x.size(1) == H && x.size(2) == W && x.size(3) >= C,
+              "hcb.preact_conv3x3_wgrad: x is not [N, H, W, >= C_in] of geom");
+  TORCH_CHECK(dz.size(0) == N && dz.size(1) == pl.P && dz.size(2) == pl.Q && dz.size(3) >= Nout,
+              "hcb.preact_conv3x3_wgrad: dz must be [N, P, Q, >= Nout] = [", N, ", ", pl.P, ", ", pl.Q, ", ", Nout, "]");
+  TORCH_CHECK(x.stride(-1) == 1 && dz.stride(-1) == 1 && x.stride(2) == ldx && dz.stride(2) == ldz,
+              "hcb.preact_conv3x3_wgrad: non-contiguous rows (channel stride must be 1, pixel stride ld)");
+  const int64_t M = N * H * W, Mz = N * pl.P * pl.Q;
+  const int64_t xb = ((M - 1) * ldx + C) * e, zb = ((Mz - 1) * ldz + Nout) * e;
+  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31), "hcb.preact_conv3x3_wgrad: tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(dz, zb, "dz");
+  check_align16(x.data_ptr(), "x");
+  check_align16(dz.data_ptr(), "dz");
+  check_cuda(dw, "dw");
+  TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.dim() == 2 && dw.size(0) == Nout && dw.stride(1) == 1 &&
+                  dw.size(1) >= 9 * C && dw.stride(0) >= 9 * C,
+              "hcb.preact_conv3x3_wgrad: dw must be float32 [Nout][>= 9 * C_in] with contiguous rows of stride >= 9 * C_in");
+  check_range(dw, ((Nout - 1) * dw.stride(0) + 9 * C) * 4, "dw");
+  check_cuda(ws, "ws");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= pl.ws_floats,
+              "hcb.preact_conv3x3_wgrad: the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ",
+              pl.ws_floats, " (preact_conv3x3_wgrad_ws)");
+  hcb::PreactWgradParams p{};
+  p.x = x.data_ptr();
+  p.dz = dz.data_ptr();
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.mean = opt_f32(mean, C, "saved_mean");
+  p.invstd = opt_f32(invstd, C, "saved_invstd");
+  p.ws = ws.data_ptr<float>();
+  p.dw = dw.data_ptr<float>();
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldz = (int)ldz;
+  p.Nout = (int)Nout; p.ldw = (int)dw.stride(0); p.stride = (int)g[7];
+  p.x_bytes = (uint32_t)xb;
+  p.dz_bytes = (uint32_t)zb;
+  hcb::launch_preact_conv3x3_wgrad(p, cur_stream(), f32);
+}
+
 // ---- dense layer data gradient with the ReLU / BatchNorm backward applied in registers (dense3x3_dgrad.hip):
 // gin += BN-backward(relu'(BN(x)) * conv3x3-dgrad(dz, w)), dgamma / dbeta overwritten. geom = [N, H, W, C, ldx,
 // ldz, ldg, Nout]: x the raw NHWC concat buffer, dz the layer's 16 channels of the block's gradient buffer and gin
@@ -2157,6 +2227,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("dense_conv3x3_wgrad(Tensor x, Tensor dz, Tensor gamma, Tensor beta, Tensor saved_mean, Tensor saved_invstd, "
         "Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
   m.def("dense_conv3x3_wgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_wgrad_ws);
+  m.def("preact_conv3x3_wgrad(Tensor x, Tensor dz, Tensor gamma, Tensor beta, Tensor saved_mean, Tensor saved_invstd, "
+        "Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
+  m.def("preact_conv3x3_wgrad_ws(int[] geom, bool f32) -> int", preact_conv3x3_wgrad_ws);
   m.def("dense_conv3x3_dgrad(Tensor x, Tensor dz, Tensor(a!) gin, Tensor w, Tensor gamma, Tensor beta, Tensor saved_mean, "
         "Tensor saved_invstd, Tensor(b!) ws, Tensor(c!) dgamma, Tensor(d!) dbeta, int[] geom) -> ()");
   m.def("dense_conv3x3_dgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_dgrad_ws);
@@ -2234,6 +2307,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("dense_conv3x3_fwd", dense_conv3x3_fwd);
   m.impl("preact_conv3x3_fwd", preact_conv3x3_fwd);
   m.impl("dense_conv3x3_wgrad", dense_conv3x3_wgrad);
+  m.impl("preact_conv3x3_wgrad", preact_conv3x3_wgrad);
   m.impl("dense_conv3x3_dgrad", dense_conv3x3_dgrad);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);

@@ -389,6 +389,34 @@ struct PreactParams {
 bool preact_conv3x3_fits(int N, int H, int W, int C, int Nout, int stride, bool f32);
 void launch_preact_conv3x3(const PreactParams& p, hipStream_t st, bool f32);
 
+// ---------------------------------------------------------------- ResNet-v2 pre-activation conv weight gradient (preact3x3_wgrad.hip)
+// dw[n][tap * C + c] += sum over output pixels of dz[pixel][n] * relu(BN(x))[pixel * stride + tap - pad][c] (3x3, TF
+// 'SAME', stride 1 | 2; C and Nout 16, 32 or 64), BN and ReLU applied on the way into LDS: x the raw NHWC block input
+// (row stride ldx), dz conv1's raw-output gradient [N][P][Q] (row stride ldz, x's type), mean / invstd the saved batch
+// statistics. Two launches without atomics: per (32-channel chunk, pixel slab) partials into ws
+// [nslabs][Nout][9][C rounded up to 32] (caller-owned, never zeroed, every element read is written first), then a
+// fold in slab order that adds into dw (fp32 [Nout][>= 9 * C], row stride ldw).
+struct PreactWgradParams {
+  const void* x;
+  const void* dz;
+  const float *gamma, *beta, *mean, *invstd;  // [C]
+  float* ws;
+  float* dw;
+  int N, H, W, C, ldx, ldz, Nout, ldw, stride;
+  uint32_t x_bytes, dz_bytes;
+  // set by the launcher
+  int P, Q, pt, pl, TR, PW, patch_pix, nit, zpix, nbuf, strips_per_img, nstrips, strips_per_slab, nslabs;
+};
+struct PreactWgradPlan {
+  int P, Q, pt, pl, TR, PW, patch_pix, nit, zpix, nbuf, strips_per_img, nstrips, strips_per_slab, nslabs;
+  size_t lds_bytes;
+  int64_t ws_floats;
+};
+// strip rows, buffering, slab count and workspace floats of this problem (a function of the shape alone); false for
+// a shape the kernel does not take or a width of which even one-row strips miss the LDS budget
+bool preact_conv3x3_wgrad_plan(int N, int H, int W, int C, int Nout, int stride, bool f32, PreactWgradPlan* out);
+void launch_preact_conv3x3_wgrad(const PreactWgradParams& p, hipStream_t st, bool f32);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

@@ -28,7 +28,13 @@ Fn.preact_conv3x3_forward: one launch, output statistics included) against bn_ap
 the existing conv GEMM (statistics in its epilogue) reading it back, on the five layer shapes of those models
 (default batch 128 there: pass --batch 128), by the same method. Neither side is charged bn_stats_acc.
 
-    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all] [--wgrad | --dgrad | --preact]
+--preact-wgrad times the weight gradient of those five layers: the fused kernel (csrc/kernels/preact3x3_wgrad.hip,
+Fn.preact_conv3x3_wgrad: two launches, partials + fold) against bn_apply_acc re-materialising the operand and
+conv_wgrad reading it back, by the same method. The fused side is not charged the fp32 path's merge of dz's Planes
+(the layer gets dz as Planes from conv1's BN backward), the unfused side not its split.
+
+    python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all]
+                                [--wgrad | --dgrad | --preact | --preact-wgrad]
 """
 import argparse
 import os
@@ -243,6 +249,59 @@ def preact_main(args):
     set_gpu_compute_dtype(torch.bfloat16)
 
 
+def preact_wgrad_main(args):
+    N = args.batch
+    print(f"# pre-activation conv weight gradient: batch {N}, {args.iters} launches per round, median of {args.rounds} "
+          "rounds, random data, warm cache")
+    print("# dtype  H  C_in Nout s | fused us  fused(A/A) us | bn apply us + wgrad us = unfused us | unfused / fused | fused GB/s")
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        set_gpu_compute_dtype(dt)
+        Fn.set_f32_native(name == "fp32")
+        e = 4 if name == "fp32" else 2
+        for H, C, nout, s in PREACT_SHAPES:
+            M, P = N * H * H, H // s
+            x = torch.randn(N, H, H, C, device="cuda").to(dt)
+            dz = torch.randn(N, P, P, nout, device="cuda").to(dt)
+            pads = Fn.same_pads(H, 3, s)
+            spec = ConvSpec(cin=C, cin_pad=C, cout=nout, kh=3, kw=3, sh=s, sw=s, pt=pads[0], pl=pads[0], pb=pads[1],
+                            pr=pads[1])
+            gamma, beta = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
+            xf = x.float().reshape(M, C)
+            acc = torch.zeros(R, 2, C, device="cuda")
+            acc[:, 0], acc[:, 1] = xf.sum(0) / R, (xf * xf).sum(0) / R
+            sv = torch.empty(2, C, device="cuda")
+            op = empty_op((N, H, H, C), "cuda")  # the re-materialised operand of the unfused chain (Planes on fp32)
+            dw = torch.zeros(nout, 9 * C, device="cuda")
+            ws = Fn.preact_wgrad_workspace(x.shape, C, nout, s, dt, "cuda")
+            dzp = Fn.to_planes(dz) if name == "fp32" else dz
+
+            def bn():
+                Fn.bn_forward_acc(x, gamma, beta, None, None, 1.0, EPS, op, True, acc, R, sv[0], sv[1])
+
+            def fused():
+                Fn.preact_conv3x3_wgrad(x, C, dz, gamma, beta, sv[0], sv[1], dw, s, ws=ws)
+
+            def wgrad():
+                Fn.conv_wgrad(dzp, op, spec, dw)
+
+            ops = {"bn": bn, "fused": fused, "fused2": fused, "conv": wgrad}
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            m = {k: statistics.median(v) for k, v in t.items()}
+            un = m["bn"] + m["conv"]
+            gbs = (M * C + N * P * P * nout) * e / (m["fused"] * 1e-6) / 1e9  # algorithmic bytes: x once, dz once
+            print(f"{name:5s} {H:3d} {C:4d} {nout:4d} {s} | {m['fused']:8.1f} {m['fused2']:8.1f} | {m['bn']:8.1f} + "
+                  f"{m['conv']:8.1f} = {un:8.1f} | {un / m['fused']:5.2f} | {gbs:6.0f}", flush=True)
+    Fn.set_f32_native(False)
+    set_gpu_compute_dtype(torch.bfloat16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -252,7 +311,10 @@ def main():
     ap.add_argument("--wgrad", action="store_true", help="the weight gradient instead of the forward pass")
     ap.add_argument("--dgrad", action="store_true", help="the data gradient with the BN-ReLU backward instead")
     ap.add_argument("--preact", action="store_true", help="the CIFAR ResNet-v2 pre-activation conv instead")
+    ap.add_argument("--preact-wgrad", action="store_true", help="the weight gradient of the pre-activation conv instead")
     args = ap.parse_args()
+    if args.preact_wgrad:
+        return preact_wgrad_main(args)
     if args.preact:
         return preact_main(args)
     if args.wgrad:
