@@ -32,7 +32,11 @@ accumulate mode in the shortcut kernel, no unfused BN reduction.
 """
 from __future__ import annotations
 
+import torch
+
+from ..nn import layers as L
 from ..nn.layers import BNReLU, ConvBN, GlobalAvgPool, Logits, PadShortcut, PreActConv, empty_act
+from ..ops import functional as Fn
 from .base import CNNModel
 
 LAYER_COUNTS = {20: (3, 3, 3), 32: (5, 5, 5), 44: (7, 7, 7), 56: (9, 9, 9), 110: (18, 18, 18)}
@@ -153,7 +157,8 @@ class PreActBasicBlock:
     """The v2 basic block: a = relu(bn(x)); conv 3x3 (stride) on a + BN + ReLU (``nn.layers.PreActConv``: one
     fused launch with FUSE_PREACT) -> conv 3x3 without BN, bias or activation, whose GEMM epilogue adds the
     shortcut; no ReLU after the add. The shortcut is taken from x, not from a: the identity, or plan A
-    (``PadShortcut``). Backward: conv1's BN-backward reduction runs in the epilogue of conv2's data gradient;
+    (``PadShortcut``). 16-bit inference runs the whole block -- both BatchNorms, both convs and the add -- as one
+    launch (``Fn.preact_block_inference``, FUSE_PREACT_BLOCK) wherever the kernel's plan fits. Backward: conv1's BN-backward reduction runs in the epilogue of conv2's data gradient;
     the shortcut's gradient (dy itself, or plan A's dx) is added in the pre-activation BN's backward apply."""
 
     def __init__(self, ps, name, in_shape, depth: int, stride: int, scratch: dict):
@@ -174,8 +179,19 @@ class PreActBasicBlock:
     def layers(self):
         return [self.pre, self.c1, self.c2]
 
+    def _one_launch(self, x) -> bool:
+        """16-bit inference on native plain tensors of a geometry the block kernel's plan fits (FUSE_PREACT_BLOCK)."""
+        return (L.FUSE_PREACT_BLOCK and not self.c1.training and Fn.native(x) and not Fn.is_planes(x)
+                and x.dtype != torch.float32
+                and Fn.preact_block_fits(x.shape, self.in_shape[2], self.out_shape[2], self.pc.stride))
+
     def forward(self, x):
         sc = self.sc.forward(x) if self.sc is not None else x
+        if self._one_launch(x):
+            pre, c1, c2 = self.pre, self.c1, self.c2
+            out = empty_act((x.shape[0],) + tuple(self.out_shape), x.device)
+            return Fn.preact_block_inference(x, c1.w.data, *pre._bn_params(), pre.eps, c2.w.data, *c1._bn_params(),
+                                             c1.eps, sc, out, self.pc.stride, wpack1=c1.pack.pack, wpack2=c2.pack.pack)
         return self.c2.forward(self.pc.forward(x), residual=sc)
 
     def backward(self, dy):

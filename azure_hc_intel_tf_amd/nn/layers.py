@@ -1297,6 +1297,14 @@ FUSE_PREACT = _env_on("HCB_FUSE_PREACT")
 # (0.55x at 8 x 8 x 64 in fp32), where its slab rule leaves few workgroups (profiles/resnet_cifar_v2_wgrad.txt).
 FUSE_PREACT_WGRAD = os.environ.get("HCB_FUSE_PREACT_WGRAD", "0") == "1"
 
+# 16-bit --forward_only: the WHOLE pre-activation basic block -- BN1, ReLU, conv1, BN2, ReLU, conv2 and the shortcut
+# add -- in one launch (csrc/kernels/preact_block.hip, Fn.preact_block_inference; models/resnet_cifar.py takes it
+# where Fn.preact_block_fits). False (``HCB_FUSE_PREACT_BLOCK=0``): bn_inference, conv_bn_inference and the conv with
+# the residual add, three launches -- the A/B partner. Training, fp32 and the ImageNet ResNet-v2 never take it. Default ON: the captured
+# resnet56_v2 --forward_only step at batch 128 runs 1.38x as fast in bf16 and 1.40x in fp16 with it (A/A 0.17 % /
+# 0.03 %; profiles/resnet_cifar_v2_block.txt).
+FUSE_PREACT_BLOCK = _env_on("HCB_FUSE_PREACT_BLOCK")
+
 
 class _PreActConv1(ConvBN):
     """conv1 of a pre-activation block: a ConvBN whose weight gradient PreActConv.backward may redirect to the fused

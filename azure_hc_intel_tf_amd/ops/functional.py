@@ -1709,6 +1709,69 @@ def preact_conv3x3_forward(x, w, gamma, beta, eps: float, out, stride: int = 1, 
     return BNSaved(saved_mean, saved_invstd) if train else None
 
 
+def preact_block_fits(shape, c_in: int, nout: int, stride: int) -> bool:
+    """Whether the one-launch inference block (preact_block_inference's kernel) takes a block input of ``shape``
+    [N, H, W, ld]: channels and stride in its sets, and a strip of the map within its tile and LDS budget."""
+    N, H, W = shape[:3]
+    if c_in not in PREACT_CHANNELS or nout not in PREACT_CHANNELS or stride not in (1, 2):
+        return False
+    return bool(_ext.ops().preact_block_fits([N, H, W, c_in, c_in, nout, nout, nout, 0, 0, int(stride)]))
+
+
+def preact_block_inference(x, w1, gamma1, beta1, rmean1, rvar1, eps1: float, w2, gamma2, beta2, rmean2, rvar2,
+                           eps2: float, res, out, stride: int = 1, wpack1=None, wpack2=None):
+    """A whole pre-activation basic block at inference, on the block's raw input ``x`` [N, H, W, ld >= c_in]:
+
+        a1  = relu(gamma1 * (x - rmean1) / sqrt(rvar1 + eps1) + beta1)
+        z1  = conv3x3_SAME(stride)(a1)                                   w1 [nout, 3, 3, c_in]
+        a2  = relu(gamma2 * (z1 - rmean2) / sqrt(rvar2 + eps2) + beta2)
+        out[..., :nout] = conv3x3_SAME(1)(a2) + res[..., :nout]          w2 [nout, 3, 3, nout]
+
+    No bias, no ReLU after the add. ``res`` and ``out`` are [N, P, Q, ld >= nout], P = ceil(H / stride), Q =
+    ceil(W / stride), of x's dtype; channels past nout of out's rows are left alone. ``out`` overlaps neither ``x``
+    nor ``res`` (``res`` may be ``x`` itself: the identity shortcut). c_in and nout are 16, 32 or 64, stride 1 or 2.
+    'SAME' is TensorFlow's (``same_pads``) and both pads belong to the ACTIVATED maps: a1 and a2 are zero outside the
+    image, not relu(shift).
+
+    GPU (csrc/kernels/preact_block.hip): ONE launch on native 16-bit tensors (not fp32, not Planes); a1, z1 and a2
+    stay on the chip, a1 and a2 rounded to 16 bits once each. ``wpack1`` / ``wpack2``: the ConvBN 16-bit packs
+    ([nout][Kpad], K = (tap, c)); without them the kernels ``w1`` / ``w2`` are packed here (dense_pack: tools and
+    tests). Scale / shift of both BatchNorms are derived in the kernel from the live parameter tensors, so a captured
+    graph sees parameters changed since capture. CPU / non-native tensors: the formula above in PyTorch at ``x``'s
+    dtype, which is the definition."""
+    N, H, W, _ = x.shape
+    nout, c_in = w1.shape[0], w1.shape[3]
+    P, Q = (H + stride - 1) // stride, (W + stride - 1) // stride
+    assert tuple(w1.shape[1:3]) == (3, 3) and tuple(w2.shape) == (nout, 3, 3, nout), \
+        "preact_block_inference: w1 is [nout, 3, 3, c_in], w2 [nout, 3, 3, nout]"
+    if native(x):
+        pdt = torch.bfloat16 if x.dtype == torch.float32 else x.dtype
+        if wpack1 is None:
+            wpack1 = dense_pack(w1, pdt)[0]
+        if wpack2 is None:
+            wpack2 = dense_pack(w2, pdt)[0]
+        x, res, out_t = _pl(x), _pl(res), _pl(out)  # (the op refuses Planes and fp32 by name)
+        _ext.ops().preact_block_inf(x, wpack1, wpack2, res, out_t,
+                                    [N, H, W, c_in, x.stride(-2), res.stride(-2), out_t.stride(-2), nout,
+                                     _round_up(9 * c_in, 64), _round_up(9 * nout, 64), int(stride)],
+                                    [gamma1, beta1, rmean1, rvar1], [gamma2, beta2, rmean2, rvar2], float(eps1), float(eps2))
+        return out
+    assert tuple(out.shape[:3]) == (N, P, Q) and out.shape[3] >= nout and tuple(res.shape[:3]) == (N, P, Q), \
+        "preact_block_inference: res and out are [N, P, Q, >= nout]"
+    dt = x.dtype
+
+    def bn_relu_conv(t, w, gamma, beta, rmean, rvar, eps, s):
+        c = w.shape[3]
+        a = torch.relu((t[..., :c] - rmean[:c].to(dt)) * (torch.rsqrt(rvar[:c] + eps) * gamma[:c]).to(dt) + beta[:c].to(dt))
+        (pt, pb), (pl, pr) = same_pads(t.shape[1], 3, s), same_pads(t.shape[2], 3, s)
+        a = F.pad(a.permute(0, 3, 1, 2), (pl, pr, pt, pb))
+        return F.conv2d(a, w.to(dt).permute(0, 3, 1, 2), stride=s).permute(0, 2, 3, 1)
+
+    z1 = bn_relu_conv(x, w1, gamma1, beta1, rmean1, rvar1, eps1, stride)
+    out[..., :nout] = bn_relu_conv(z1, w2, gamma2, beta2, rmean2, rvar2, eps2, 1) + res[..., :nout]
+    return out
+
+
 def preact_wgrad_workspace(shape, c_in: int, nout: int, stride: int, dtype, device):
     """The caller-owned workspace of preact_conv3x3_wgrad for a block input of ``shape`` [N, H, W, ld]:
     [slabs * nout * 9 * round_up(c_in, 32)] fp32, never zeroed. The slab count depends on the shape alone."""

@@ -1686,6 +1686,103 @@ void preact_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Te
   hcb::launch_preact_conv3x3(p, cur_stream(), f32);
 }
 
+// ---- ResNet-v2 pre-activation basic block, 16-bit inference (preact_block.hip): out = conv3x3_SAME(1)(relu(bn2(
+// conv3x3_SAME(stride)(relu(bn1(x)))))) + res in one launch. geom = [N, H, W, C, ldx, ldr, ldo, Nout, Kpad1, Kpad2,
+// stride]: x the raw NHWC block input, res / out NHWC of ceil(H / stride) x ceil(W / stride) pixels and x's type;
+// w1 / w2 the [Nout][Kpad] 16-bit packs; bn1 / bn2 = [gamma, beta, moving mean, moving variance] (fp32, live)
+static bool preact_block_geom_fits(at::IntArrayRef g) {
+  TORCH_CHECK(g.size() == 11, "hcb.preact_block_inf: geom = [N, H, W, C, ldx, ldr, ldo, Nout, Kpad1, Kpad2, stride]");
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], Nout = g[7], s = g[10];
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.preact_block_inf: empty tensor");
+  TORCH_CHECK(C == 16 || C == 32 || C == 64, "hcb.preact_block_inf: C_in must be 16, 32 or 64, got ", C);
+  TORCH_CHECK(Nout == 16 || Nout == 32 || Nout == 64, "hcb.preact_block_inf: Nout must be 16, 32 or 64, got ", Nout);
+  TORCH_CHECK(s == 1 || s == 2, "hcb.preact_block_inf: stride must be 1 or 2, got ", s);
+  return H < (1 << 20) && W < (1 << 20) && hcb::preact_block_fits((int)N, (int)H, (int)W, (int)C, (int)Nout, (int)s);
+}
+
+bool preact_block_fits(at::IntArrayRef g) { return preact_block_geom_fits(g); }
+
+void preact_block_inf(const Tensor& x, const Tensor& w1, const Tensor& w2, const Tensor& res, const Tensor& out,
+                      at::IntArrayRef g, at::TensorList bn1, at::TensorList bn2, double eps1, double eps2) {
+  check_cuda(x, "x");
+  check_cuda(res, "res");
+  check_cuda(out, "out");
+  TORCH_CHECK(x.scalar_type() != at::kFloat && res.scalar_type() != at::kFloat && out.scalar_type() != at::kFloat,
+              "hcb.preact_block_inf: float32 tensors are not taken (16-bit inference only; fp32 runs preact_conv3x3_fwd)");
+  TORCH_CHECK(x.dim() == 4 && res.dim() == 4 && out.dim() == 4,
+              "hcb.preact_block_inf: x, res and out are plain [N, H, W, C] tensors (not Planes)");
+  TORCH_CHECK(res.scalar_type() == x.scalar_type() && out.scalar_type() == x.scalar_type(),
+              "hcb.preact_block_inf: x, res and out dtypes differ");
+  check_act(x, "x");
+  check_act(w1, "w1");
+  check_act(w2, "w2");
+  const bool fits = preact_block_geom_fits(g);
+  const int64_t N = g[0], H = g[1], W = g[2], C = g[3], ldx = g[4], ldr = g[5], ldo = g[6], Nout = g[7], Kpad1 = g[8],
+                Kpad2 = g[9], s = g[10];
+  TORCH_CHECK(ldx % 8 == 0 && ldr % 8 == 0 && ldo % 8 == 0, "hcb.preact_block_inf: ld must be a multiple of 8, got ", ldx,
+              " / ", ldr, " / ", ldo);
+  TORCH_CHECK(ldx >= C && ldr >= Nout && ldo >= Nout, "hcb.preact_block_inf: rows of ", ldx, " / ", ldr, " / ", ldo,
+              " channels do not hold C_in = ", C, " / Nout = ", Nout);
+  const int64_t P = (H + s - 1) / s, Q = (W + s - 1) / s;
+  TORCH_CHECK(x.size(0) == N && x.size(1) == H && x.size(2) == W && x.size(3) >= C,
+              "hcb.preact_block_inf: x is not [N, H, W, >= C_in] of geom");
+  for (const Tensor* t : {&res, &out})
+    TORCH_CHECK(t->size(0) == N && t->size(1) == P && t->size(2) == Q && t->size(3) >= Nout, "hcb.preact_block_inf: ",
+                t == &res ? "res" : "out", " must be [N, P, Q, >= Nout] = [", N, ", ", P, ", ", Q, ", ", Nout, "]");
+  const auto rows_ok = [](const Tensor& t, int64_t ld) {
+    return t.stride(3) == 1 && t.stride(2) == ld && t.stride(1) == ld * t.size(2) && t.stride(0) == ld * t.size(2) * t.size(1);
+  };
+  TORCH_CHECK(rows_ok(x, ldx) && rows_ok(res, ldr) && rows_ok(out, ldo),
+              "hcb.preact_block_inf: non-contiguous rows (channel stride must be 1, pixel stride ld)");
+  TORCH_CHECK(Kpad1 % 8 == 0 && Kpad1 >= 9 * C && Kpad2 % 8 == 0 && Kpad2 >= 9 * Nout,
+              "hcb.preact_block_inf: Kpad must be a multiple of 8 >= 9 * channels");
+  TORCH_CHECK(fits, "hcb.preact_block_inf: ", H, " x ", W, " x ", C, " -> ", Nout, " at stride ", s,
+              " does not fit the strip, patch and LDS budget of the kernel");
+  const int64_t xb = ((N * H * W - 1) * ldx + C) * 2, rb = ((N * P * Q - 1) * ldr + Nout) * 2,
+                ob = ((N * P * Q - 1) * ldo + Nout) * 2, w1b = Nout * Kpad1 * 2, w2b = Nout * Kpad2 * 2;
+  TORCH_CHECK(xb < (1ll << 31) && rb < (1ll << 31) && ob < (1ll << 31),
+              "hcb.preact_block_inf: tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(x, xb, "x");
+  check_range(res, rb, "res");
+  check_range(out, ob, "out");
+  check_range(w1, w1b, "w1");
+  check_range(w2, w2b, "w2");
+  check_align16(x.data_ptr(), "x");
+  check_align16(res.data_ptr(), "res");
+  check_align16(out.data_ptr(), "out");
+  check_align16(w1.data_ptr(), "w1");
+  check_align16(w2.data_ptr(), "w2");
+  const char *xp = (const char*)x.data_ptr(), *rp = (const char*)res.data_ptr(), *op = (const char*)out.data_ptr();
+  TORCH_CHECK(!(xp < op + ob && op < xp + xb), "hcb.preact_block_inf: out aliases x (other workgroups still read the halo)");
+  TORCH_CHECK(!(rp < op + ob && op < rp + rb), "hcb.preact_block_inf: out aliases res");
+  TORCH_CHECK(bn1.size() == 4 && bn2.size() == 4,
+              "hcb.preact_block_inf: bn1 / bn2 = [gamma, beta, moving mean, moving variance]");
+  const float* v[8];
+  for (int i = 0; i < 8; ++i) {
+    const Tensor& t = i < 4 ? bn1[i] : bn2[i - 4];
+    check_f32(t, i < 4 ? "bn1" : "bn2");
+    TORCH_CHECK(t.is_contiguous() && t.numel() >= (i < 4 ? C : Nout), "hcb.preact_block_inf: ", i < 4 ? "bn1" : "bn2",
+                " vectors must be contiguous with one value per channel");
+    v[i] = t.data_ptr<float>();
+  }
+  hcb::PreactBlockParams p{};
+  p.x = x.data_ptr();
+  p.res = res.data_ptr();
+  p.out = out.data_ptr();
+  p.w1 = w1.data_ptr();
+  p.w2 = w2.data_ptr();
+  p.gamma1 = v[0]; p.beta1 = v[1]; p.mean1 = v[2]; p.var1 = v[3];
+  p.gamma2 = v[4]; p.beta2 = v[5]; p.mean2 = v[6]; p.var2 = v[7];
+  p.eps1 = (float)eps1;
+  p.eps2 = (float)eps2;
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldr = (int)ldr; p.ldo = (int)ldo;
+  p.Nout = (int)Nout; p.Kpad1 = (int)Kpad1; p.Kpad2 = (int)Kpad2; p.stride = (int)s;
+  p.x_bytes = (uint32_t)xb;
+  p.w1_bytes = (uint32_t)w1b;
+  p.w2_bytes = (uint32_t)w2b;
+  hcb::launch_preact_block(p, cur_stream());
+}
+
 // ---- dense layer weight gradient (dense3x3_wgrad.hip): dw[n][tap * C + c] += sum dz[.., slot + n] *
 // relu(BN(x[.., c])) shifted by the tap. geom = [N, H, W, C, ldx, slot, ldz, Nout]: x the raw NHWC concat
 // buffer, dz the layer's 16 channels of the block's gradient buffer (a view: rows of ldz channels, the
@@ -2230,6 +2327,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("preact_conv3x3_wgrad(Tensor x, Tensor dz, Tensor gamma, Tensor beta, Tensor saved_mean, Tensor saved_invstd, "
         "Tensor(a!) ws, Tensor(b!) dw, int[] geom) -> ()");
   m.def("preact_conv3x3_wgrad_ws(int[] geom, bool f32) -> int", preact_conv3x3_wgrad_ws);
+  m.def("preact_block_inf(Tensor x, Tensor w1, Tensor w2, Tensor res, Tensor(a!) out, int[] geom, Tensor[] bn1, "
+        "Tensor[] bn2, float eps1, float eps2) -> ()");
+  m.def("preact_block_fits(int[] geom) -> bool", preact_block_fits);
   m.def("dense_conv3x3_dgrad(Tensor x, Tensor dz, Tensor(a!) gin, Tensor w, Tensor gamma, Tensor beta, Tensor saved_mean, "
         "Tensor saved_invstd, Tensor(b!) ws, Tensor(c!) dgamma, Tensor(d!) dbeta, int[] geom) -> ()");
   m.def("dense_conv3x3_dgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_dgrad_ws);
@@ -2308,6 +2408,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("preact_conv3x3_fwd", preact_conv3x3_fwd);
   m.impl("dense_conv3x3_wgrad", dense_conv3x3_wgrad);
   m.impl("preact_conv3x3_wgrad", preact_conv3x3_wgrad);
+  m.impl("preact_block_inf", preact_block_inf);
   m.impl("dense_conv3x3_dgrad", dense_conv3x3_dgrad);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);

@@ -417,6 +417,27 @@ struct PreactWgradPlan {
 bool preact_conv3x3_wgrad_plan(int N, int H, int W, int C, int Nout, int stride, bool f32, PreactWgradPlan* out);
 void launch_preact_conv3x3_wgrad(const PreactWgradParams& p, hipStream_t st, bool f32);
 
+// ---------------------------------------------------------------- ResNet-v2 pre-activation basic block, inference (preact_block.hip)
+// out = conv3x3_SAME(1)(relu(bn2(conv3x3_SAME(stride)(relu(bn1(x)))))) + res in ONE launch, 16-bit tensors only: x the
+// raw NHWC block input (row stride ldx), res / out NHWC [N][P][Q] (row strides ldr / ldo, P x Q = ceil(H / stride) x
+// ceil(W / stride)), w1 [Nout][Kpad1] / w2 [Nout][Kpad2] the 16-bit packs (K = (tap, c)). Both BatchNorms take their
+// moving statistics; scale / shift are derived in the kernel from the live vectors. C and Nout are 16, 32 or 64.
+struct PreactBlockParams {
+  const void* x;
+  const void* res;
+  void* out;
+  const void *w1, *w2;
+  const float *gamma1, *beta1, *mean1, *var1;  // [C]
+  const float *gamma2, *beta2, *mean2, *var2;  // [Nout]
+  float eps1, eps2;
+  int N, H, W, C, ldx, ldr, ldo, Nout, Kpad1, Kpad2, stride;
+  uint32_t x_bytes, w1_bytes, w2_bytes;
+  int P, Q, pt, pl, TR, strips_per_img, PW, patch_pix, AW, a2_pix;  // set by the launcher
+};
+// whether the shape is one the kernel takes and a one-row strip of it fits the LDS and tile budget
+bool preact_block_fits(int N, int H, int W, int C, int Nout, int stride);
+void launch_preact_block(const PreactBlockParams& p, hipStream_t st);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

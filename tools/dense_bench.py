@@ -33,8 +33,13 @@ Fn.preact_conv3x3_wgrad: two launches, partials + fold) against bn_apply_acc re-
 conv_wgrad reading it back, by the same method. The fused side is not charged the fp32 path's merge of dz's Planes
 (the layer gets dz as Planes from conv1's BN backward), the unfused side not its split.
 
+--preact-block times the whole pre-activation block of 16-bit inference on those five geometries: the one-launch
+kernel (csrc/kernels/preact_block.hip, Fn.preact_block_inference) against today's chain -- bn_inference,
+conv_bn_inference and the conv with the residual add -- in bf16 and fp16, by the same method. shortcut_pad_fwd, which
+both sides run on the two stride-2 blocks, is timed beside them and charged to neither.
+
     python tools/dense_bench.py [--batch 64] [--iters 20] [--rounds 7] [--all]
-                                [--wgrad | --dgrad | --preact | --preact-wgrad]
+                                [--wgrad | --dgrad | --preact | --preact-wgrad | --preact-block]
 """
 import argparse
 import os
@@ -302,6 +307,65 @@ def preact_wgrad_main(args):
     set_gpu_compute_dtype(torch.bfloat16)
 
 
+def preact_block_main(args):
+    N = args.batch
+    print(f"# pre-activation block, 16-bit inference: batch {N}, {args.iters} launches per round, median of {args.rounds} "
+          "rounds, random data, warm cache")
+    print("# dtype  H  C_in Nout s | block us  block(A/A) us | bn us + conv1 us + conv2 us (+ pad us) = chain us | "
+          "chain / block | block GB/s")
+    for name, dt in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
+        set_gpu_compute_dtype(dt)
+        for H, C, nout, s in PREACT_SHAPES:
+            P = H // s
+            x = torch.randn(N, H, H, C, device="cuda").to(dt)
+            pads = Fn.same_pads(H, 3, s)
+            s1 = ConvSpec(cin=C, cin_pad=C, cout=nout, kh=3, kw=3, sh=s, sw=s, pt=pads[0], pl=pads[0], pb=pads[1], pr=pads[1])
+            s2 = ConvSpec(cin=nout, cin_pad=nout, cout=nout, kh=3, kw=3, pt=1, pl=1, pb=1, pr=1)
+            w1 = torch.randn(nout, 3, 3, C, device="cuda") * (2.0 / 9 / C) ** 0.5
+            w2 = torch.randn(nout, 3, 3, nout, device="cuda") * (2.0 / 9 / nout) ** 0.5
+            pk1, pk2 = Fn.dense_pack(w1, dt)[0], Fn.dense_pack(w2, dt)[0]
+            bn1, bn2 = [[torch.rand(c, device="cuda") + 0.5, torch.randn(c, device="cuda") * 0.1,
+                         torch.randn(c, device="cuda") * 0.1, torch.rand(c, device="cuda") + 0.5] for c in (C, nout)]
+            a1 = empty_act((N, H, H, C), "cuda")
+            a2, res, out = (empty_act((N, P, P, nout), "cuda") for _ in range(3))
+            res.copy_(torch.randn(N, P, P, nout, device="cuda"))
+
+            def block():
+                Fn.preact_block_inference(x, w1, *bn1, EPS, w2, *bn2, EPS, res if C != nout else x, out, s, wpack1=pk1,
+                                          wpack2=pk2)
+
+            def bn():
+                Fn.bn_inference(x, *bn1, EPS, a1, True)
+
+            def conv1():
+                Fn.conv_bn_inference(a1, s1, pk1, w1, *bn2, EPS, a2, True)
+
+            def conv2():
+                Fn.conv_forward(a2, s2, pk2, w2, out, residual=res if C != nout else x)
+
+            def pad():
+                Fn.shortcut_pad_forward(x, res, s)
+
+            ops = {"block": block, "block2": block, "bn": bn, "conv1": conv1, "conv2": conv2}
+            if C != nout:
+                ops["pad"] = pad  # (both sides run it on the two stride-2 blocks; the chain is not charged it)
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            m = {k: statistics.median(v) for k, v in t.items()}
+            un = m["bn"] + m["conv1"] + m["conv2"]
+            gbs = (N * H * H * C + 2 * N * P * P * nout) * 2 / (m["block"] * 1e-6) / 1e9  # x once, res once, out once
+            print(f"{name:5s} {H:3d} {C:4d} {nout:4d} {s} | {m['block']:8.1f} {m['block2']:8.1f} | {m['bn']:8.1f} + "
+                  f"{m['conv1']:8.1f} + {m['conv2']:8.1f} (+ {m.get('pad', 0.0):5.1f}) = {un:8.1f} | {un / m['block']:5.2f} | "
+                  f"{gbs:6.0f}", flush=True)
+    set_gpu_compute_dtype(torch.bfloat16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -312,7 +376,10 @@ def main():
     ap.add_argument("--dgrad", action="store_true", help="the data gradient with the BN-ReLU backward instead")
     ap.add_argument("--preact", action="store_true", help="the CIFAR ResNet-v2 pre-activation conv instead")
     ap.add_argument("--preact-wgrad", action="store_true", help="the weight gradient of the pre-activation conv instead")
+    ap.add_argument("--preact-block", action="store_true", help="the one-launch 16-bit inference block against its chain")
     args = ap.parse_args()
+    if args.preact_block:
+        return preact_block_main(args)
     if args.preact_wgrad:
         return preact_wgrad_main(args)
     if args.preact:
