@@ -260,6 +260,93 @@ const float* opt_f32(const c10::optional<Tensor>& t, int64_t n, const char* what
   return t->data_ptr<float>();
 }
 
+// ---- the checks the patch-resident BN-ReLU 3x3 ops share (csrc/kernels/patch3x3.h); `op` names the op in messages
+
+// an operand addressed with 32-bit byte offsets: below 2 GiB, inside its storage, 16-byte aligned
+void check_act_rows(const char* op, const Tensor& t, int64_t bytes, const char* name) {
+  TORCH_CHECK(bytes < (1ll << 31), "hcb.", op, ": tensors must stay below 2 GiB (32-bit offsets)");
+  check_range(t, bytes, name);
+  check_align16(t.data_ptr(), name);
+}
+
+// the [Nout][Kpad] pack of a forward op: 16-bit, or (fp32) the bf16 hi pack with w_lo = [2][n] mid / lo packs
+template <typename P>  // DenseParams, PreactParams
+void attach_w_planes(const char* op, P& p, const Tensor& w, const c10::optional<Tensor>& w_lo, bool f32) {
+  p.w = w.data_ptr();
+  if (!f32) return;
+  TORCH_CHECK(w_lo.has_value() && w_lo->dim() == 2 && w_lo->size(0) == 2 && w_lo->stride(1) == 1 &&
+                  w_lo->scalar_type() == w.scalar_type() && w_lo->size(1) >= (int64_t)p.Nout * p.Kpad,
+              "hcb.", op, ": fp32 needs w_lo = [2][>= Nout*Kpad] of the pack's type");
+  check_cuda(*w_lo, "w_lo");
+  const Tensor m = w_lo->select(0, 0), l = w_lo->select(0, 1);
+  check_align16(m.data_ptr(), "w_lo[0]");
+  check_align16(l.data_ptr(), "w_lo[1]");
+  p.w_mid = m.data_ptr();
+  p.w_lo = l.data_ptr();
+}
+
+// the input BatchNorm of a forward op: the R replicas of x's statistics, the layer's vectors, what it publishes
+template <typename P>
+void attach_bn_in(const char* op, P& p, const Tensor& acc, int64_t R, const Tensor& gamma,
+                  const Tensor& beta, const c10::optional<Tensor>& shift, double eps, double momentum,
+                  const c10::optional<Tensor>& saved_mean, const c10::optional<Tensor>& saved_invstd,
+                  const c10::optional<Tensor>& run_mean, const c10::optional<Tensor>& run_var) {
+  const int64_t C = p.C;
+  check_f32(acc, "acc");
+  TORCH_CHECK(R >= 1 && acc.dim() == 3 && acc.is_contiguous() && acc.size(0) >= R && acc.size(1) == 2 && acc.size(2) >= C,
+              "hcb.", op, ": acc must be contiguous [>= R][2][>= C_in]");
+  p.acc = acc.data_ptr<float>();
+  p.R = (int)R;
+  p.acc_C = (int)acc.size(2);
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.shift = opt_f32(shift, C, "shift");
+  p.eps = (float)eps;
+  p.momentum = (float)momentum;
+  p.saved_mean = const_cast<float*>(opt_f32(saved_mean, C, "saved_mean"));
+  p.saved_invstd = const_cast<float*>(opt_f32(saved_invstd, C, "saved_invstd"));
+  TORCH_CHECK(run_mean.has_value() == run_var.has_value(), "hcb.", op, ": moving mean and variance come together");
+  p.run_mean = const_cast<float*>(opt_f32(run_mean, C, "run_mean"));
+  p.run_var = const_cast<float*>(opt_f32(run_var, C, "run_var"));
+}
+
+// the replicas that receive a forward op's output statistics at columns stats_off .. + width (`cols`: the bound as
+// the message words it). The aliasing rule against acc differs per op and stays with the caller
+template <typename P>
+void attach_out_stats(const char* op, P& p, const c10::optional<Tensor>& stats, int64_t stats_R,
+                      int64_t stats_off, int64_t width, const char* cols, const c10::optional<Tensor>& stats_shift) {
+  if (!stats.has_value()) {
+    TORCH_CHECK(!stats_shift.has_value(), "hcb.", op, ": stats_shift without stats");
+    return;
+  }
+  check_f32(*stats, "stats");
+  TORCH_CHECK(stats_R >= 1 && stats->dim() == 3 && stats->is_contiguous() && stats->size(0) >= stats_R &&
+                  stats->size(1) == 2 && stats_off >= 0 && stats_off + width <= stats->size(2),
+              "hcb.", op, ": stats must be contiguous [>= stats_R][2][>= ", cols, "]");
+  p.stats = stats->data_ptr<float>() + stats_off;
+  p.stats_R = (int)stats_R;
+  p.stats_C = (int)stats->size(2);
+  p.stats_shift = opt_f32(stats_shift, p.Nout, "stats_shift");
+}
+
+// the saved BatchNorm of a backward op (DenseWgradParams, PreactWgradParams, DenseDgradParams)
+template <typename P>
+void attach_saved_bn(P& p, int64_t C, const Tensor& gamma, const Tensor& beta, const Tensor& mean, const Tensor& invstd) {
+  p.gamma = opt_f32(gamma, C, "gamma");
+  p.beta = opt_f32(beta, C, "beta");
+  p.mean = opt_f32(mean, C, "saved_mean");
+  p.invstd = opt_f32(invstd, C, "saved_invstd");
+}
+
+// the caller-owned fp32 workspace of a backward op, `need` floats as <op>_ws reports
+float* check_ws(const char* op, const Tensor& ws, int64_t need) {
+  check_cuda(ws, "ws");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= need, "hcb.", op,
+              ": the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ", need, " (", op,
+              "_ws)");
+  return ws.data_ptr<float>();
+}
+
 void conv_igemm(const Tensor& x, const Tensor& w, const Tensor& y, const c10::optional<Tensor>& yres,
                 const c10::optional<Tensor>& bias, const c10::optional<Tensor>& stats,
                 at::IntArrayRef g, int64_t cfg, const c10::optional<Tensor>& stats_shift) {
@@ -1530,65 +1617,24 @@ void dense_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Ten
               "hcb.dense_conv3x3_fwd: W = ", W, " with C_in = ", C, " is larger than the input patch the LDS budget allows");
   const int64_t M = N * H * W;
   const int64_t xb = ((M - 1) * ldx + C) * e, yb = ((M - 1) * ldy + slot + 16) * e, wb = Nout * Kpad * 2;
-  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31) && wb < (1ll << 31),
-              "hcb.dense_conv3x3_fwd: tensors must stay below 2 GiB (32-bit offsets)");
-  check_range(x, xb, "x");
-  check_range(y, yb, "y");
-  check_range(w, wb, "w");
-  check_align16(x.data_ptr(), "x");
-  check_align16(y.data_ptr(), "y");
-  check_align16(w.data_ptr(), "w");
+  const char* op = "dense_conv3x3_fwd";
+  check_act_rows(op, x, xb, "x");
+  check_act_rows(op, y, yb, "y");
+  check_act_rows(op, w, wb, "w");
   // one buffer (or overlapping ones): the slot must not be one of the channels other workgroups still read
   const char *xp = (const char*)x.data_ptr(), *yp = (const char*)y.data_ptr();
   if (xp < yp + yb && yp < xp + xb)
     TORCH_CHECK(xp == yp && ldx == ldy && slot >= C, "hcb.dense_conv3x3_fwd: x and y overlap: one buffer, slot >= C_in");
   hcb::DenseParams p{};
-  p.x = x.data_ptr();
-  p.y = (char*)y.data_ptr() + slot * e;
-  p.w = w.data_ptr();
-  if (f32) {
-    TORCH_CHECK(w_lo.has_value() && w_lo->dim() == 2 && w_lo->size(0) == 2 && w_lo->stride(1) == 1 &&
-                    w_lo->scalar_type() == w.scalar_type() && w_lo->size(1) >= Nout * Kpad,
-                "hcb.dense_conv3x3_fwd: fp32 needs w_lo = [2][>= Nout*Kpad] of the pack's type");
-    check_cuda(*w_lo, "w_lo");
-    const Tensor m = w_lo->select(0, 0), l = w_lo->select(0, 1);
-    check_align16(m.data_ptr(), "w_lo[0]");
-    check_align16(l.data_ptr(), "w_lo[1]");
-    p.w_mid = m.data_ptr();
-    p.w_lo = l.data_ptr();
-  }
-  check_f32(acc, "acc");
-  TORCH_CHECK(R >= 1 && acc.dim() == 3 && acc.is_contiguous() && acc.size(0) >= R && acc.size(1) == 2 && acc.size(2) >= C,
-              "hcb.dense_conv3x3_fwd: acc must be contiguous [>= R][2][>= C_in]");
-  p.acc = acc.data_ptr<float>();
-  p.R = (int)R;
-  p.acc_C = (int)acc.size(2);
-  p.gamma = opt_f32(gamma, C, "gamma");
-  p.beta = opt_f32(beta, C, "beta");
-  p.shift = opt_f32(shift, C, "shift");
-  p.eps = (float)eps;
-  p.momentum = (float)momentum;
-  p.saved_mean = const_cast<float*>(opt_f32(saved_mean, C, "saved_mean"));
-  p.saved_invstd = const_cast<float*>(opt_f32(saved_invstd, C, "saved_invstd"));
-  TORCH_CHECK(run_mean.has_value() == run_var.has_value(), "hcb.dense_conv3x3_fwd: moving mean and variance come together");
-  p.run_mean = const_cast<float*>(opt_f32(run_mean, C, "run_mean"));
-  p.run_var = const_cast<float*>(opt_f32(run_var, C, "run_var"));
-  if (stats.has_value()) {
-    check_f32(*stats, "stats");
-    TORCH_CHECK(stats_R >= 1 && stats->dim() == 3 && stats->is_contiguous() && stats->size(0) >= stats_R &&
-                    stats->size(1) == 2 && stats_off >= 0 && stats_off + 16 <= stats->size(2),
-                "hcb.dense_conv3x3_fwd: stats must be contiguous [>= stats_R][2][>= stats_off + 16]");
-    TORCH_CHECK(stats->data_ptr() != acc.data_ptr() || stats_off >= C,
-                "hcb.dense_conv3x3_fwd: the slot's statistics columns must lie beyond the C_in columns read");
-    p.stats = stats->data_ptr<float>() + stats_off;
-    p.stats_R = (int)stats_R;
-    p.stats_C = (int)stats->size(2);
-    p.stats_shift = opt_f32(stats_shift, Nout, "stats_shift");
-  } else {
-    TORCH_CHECK(!stats_shift.has_value(), "hcb.dense_conv3x3_fwd: stats_shift without stats");
-  }
   p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldy = (int)ldy;
   p.Nout = (int)Nout; p.Kpad = (int)Kpad;
+  p.x = x.data_ptr();
+  p.y = (char*)y.data_ptr() + slot * e;
+  attach_w_planes(op, p, w, w_lo, f32);
+  attach_bn_in(op, p, acc, R, gamma, beta, shift, eps, momentum, saved_mean, saved_invstd, run_mean, run_var);
+  attach_out_stats(op, p, stats, stats_R, stats_off, 16, "stats_off + 16", stats_shift);
+  TORCH_CHECK(!stats.has_value() || stats->data_ptr() != acc.data_ptr() || stats_off >= C,
+              "hcb.dense_conv3x3_fwd: the slot's statistics columns must lie beyond the C_in columns read");
   p.x_bytes = (uint32_t)xb;
   p.w_bytes = (uint32_t)wb;
   hcb::launch_dense_conv3x3(p, cur_stream(), f32);
@@ -1625,62 +1671,22 @@ void preact_conv3x3_fwd(const Tensor& x, const Tensor& w, const c10::optional<Te
               "hcb.preact_conv3x3_fwd: W = ", W, " with Nout = ", Nout, " is larger than the strip and patch the LDS budget allows");
   const int64_t P = (H + s - 1) / s, Q = (W + s - 1) / s;
   const int64_t xb = ((N * H * W - 1) * ldx + C) * e, yb = ((N * P * Q - 1) * ldy + Nout) * e, wb = Nout * Kpad * 2;
-  TORCH_CHECK(xb < (1ll << 31) && yb < (1ll << 31) && wb < (1ll << 31),
-              "hcb.preact_conv3x3_fwd: tensors must stay below 2 GiB (32-bit offsets)");
-  check_range(x, xb, "x");
-  check_range(y, yb, "y");
-  check_range(w, wb, "w");
-  check_align16(x.data_ptr(), "x");
-  check_align16(y.data_ptr(), "y");
-  check_align16(w.data_ptr(), "w");
+  const char* op = "preact_conv3x3_fwd";
+  check_act_rows(op, x, xb, "x");
+  check_act_rows(op, y, yb, "y");
+  check_act_rows(op, w, wb, "w");
   const char *xp = (const char*)x.data_ptr(), *yp = (const char*)y.data_ptr();
   TORCH_CHECK(!(xp < yp + yb && yp < xp + xb), "hcb.preact_conv3x3_fwd: y aliases x (other workgroups still read the halo)");
   hcb::PreactParams p{};
-  p.x = x.data_ptr();
-  p.y = y.data_ptr();
-  p.w = w.data_ptr();
-  if (f32) {
-    TORCH_CHECK(w_lo.has_value() && w_lo->dim() == 2 && w_lo->size(0) == 2 && w_lo->stride(1) == 1 &&
-                    w_lo->scalar_type() == w.scalar_type() && w_lo->size(1) >= Nout * Kpad,
-                "hcb.preact_conv3x3_fwd: fp32 needs w_lo = [2][>= Nout*Kpad] of the pack's type");
-    check_cuda(*w_lo, "w_lo");
-    const Tensor m = w_lo->select(0, 0), l = w_lo->select(0, 1);
-    check_align16(m.data_ptr(), "w_lo[0]");
-    check_align16(l.data_ptr(), "w_lo[1]");
-    p.w_mid = m.data_ptr();
-    p.w_lo = l.data_ptr();
-  }
-  check_f32(acc, "acc");
-  TORCH_CHECK(R >= 1 && acc.dim() == 3 && acc.is_contiguous() && acc.size(0) >= R && acc.size(1) == 2 && acc.size(2) >= C,
-              "hcb.preact_conv3x3_fwd: acc must be contiguous [>= R][2][>= C_in]");
-  p.acc = acc.data_ptr<float>();
-  p.R = (int)R;
-  p.acc_C = (int)acc.size(2);
-  p.gamma = opt_f32(gamma, C, "gamma");
-  p.beta = opt_f32(beta, C, "beta");
-  p.shift = opt_f32(shift, C, "shift");
-  p.eps = (float)eps;
-  p.momentum = (float)momentum;
-  p.saved_mean = const_cast<float*>(opt_f32(saved_mean, C, "saved_mean"));
-  p.saved_invstd = const_cast<float*>(opt_f32(saved_invstd, C, "saved_invstd"));
-  TORCH_CHECK(run_mean.has_value() == run_var.has_value(), "hcb.preact_conv3x3_fwd: moving mean and variance come together");
-  p.run_mean = const_cast<float*>(opt_f32(run_mean, C, "run_mean"));
-  p.run_var = const_cast<float*>(opt_f32(run_var, C, "run_var"));
-  if (stats.has_value()) {
-    check_f32(*stats, "stats");
-    TORCH_CHECK(stats_R >= 1 && stats->dim() == 3 && stats->is_contiguous() && stats->size(0) >= stats_R &&
-                    stats->size(1) == 2 && stats->size(2) >= Nout,
-                "hcb.preact_conv3x3_fwd: stats must be contiguous [>= stats_R][2][>= Nout]");
-    TORCH_CHECK(stats->data_ptr() != acc.data_ptr(), "hcb.preact_conv3x3_fwd: stats and acc must be different accumulators");
-    p.stats = stats->data_ptr<float>();
-    p.stats_R = (int)stats_R;
-    p.stats_C = (int)stats->size(2);
-    p.stats_shift = opt_f32(stats_shift, Nout, "stats_shift");
-  } else {
-    TORCH_CHECK(!stats_shift.has_value(), "hcb.preact_conv3x3_fwd: stats_shift without stats");
-  }
   p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldy = (int)ldy;
   p.Nout = (int)Nout; p.Kpad = (int)Kpad; p.stride = (int)s;
+  p.x = x.data_ptr();
+  p.y = y.data_ptr();
+  attach_w_planes(op, p, w, w_lo, f32);
+  attach_bn_in(op, p, acc, R, gamma, beta, shift, eps, momentum, saved_mean, saved_invstd, run_mean, run_var);
+  attach_out_stats(op, p, stats, stats_R, 0, Nout, "Nout", stats_shift);
+  TORCH_CHECK(!stats.has_value() || stats->data_ptr() != acc.data_ptr(),
+              "hcb.preact_conv3x3_fwd: stats and acc must be different accumulators");
   p.x_bytes = (uint32_t)xb;
   p.w_bytes = (uint32_t)wb;
   hcb::launch_preact_conv3x3(p, cur_stream(), f32);
@@ -1740,18 +1746,11 @@ void preact_block_inf(const Tensor& x, const Tensor& w1, const Tensor& w2, const
               " does not fit the strip, patch and LDS budget of the kernel");
   const int64_t xb = ((N * H * W - 1) * ldx + C) * 2, rb = ((N * P * Q - 1) * ldr + Nout) * 2,
                 ob = ((N * P * Q - 1) * ldo + Nout) * 2, w1b = Nout * Kpad1 * 2, w2b = Nout * Kpad2 * 2;
-  TORCH_CHECK(xb < (1ll << 31) && rb < (1ll << 31) && ob < (1ll << 31),
-              "hcb.preact_block_inf: tensors must stay below 2 GiB (32-bit offsets)");
-  check_range(x, xb, "x");
-  check_range(res, rb, "res");
-  check_range(out, ob, "out");
-  check_range(w1, w1b, "w1");
-  check_range(w2, w2b, "w2");
-  check_align16(x.data_ptr(), "x");
-  check_align16(res.data_ptr(), "res");
-  check_align16(out.data_ptr(), "out");
-  check_align16(w1.data_ptr(), "w1");
-  check_align16(w2.data_ptr(), "w2");
+  check_act_rows("preact_block_inf", x, xb, "x");
+  check_act_rows("preact_block_inf", res, rb, "res");
+  check_act_rows("preact_block_inf", out, ob, "out");
+  check_act_rows("preact_block_inf", w1, w1b, "w1");
+  check_act_rows("preact_block_inf", w2, w2b, "w2");
   const char *xp = (const char*)x.data_ptr(), *rp = (const char*)res.data_ptr(), *op = (const char*)out.data_ptr();
   TORCH_CHECK(!(xp < op + ob && op < xp + xb), "hcb.preact_block_inf: out aliases x (other workgroups still read the halo)");
   TORCH_CHECK(!(rp < op + ob && op < rp + rb), "hcb.preact_block_inf: out aliases res");
@@ -1820,28 +1819,18 @@ void dense_conv3x3_wgrad(const Tensor& x, const Tensor& dz, const Tensor& gamma,
               "hcb.dense_conv3x3_wgrad: non-contiguous rows (channel stride must be 1)");
   const int64_t M = N * H * W;
   const int64_t xb = ((M - 1) * ldx + C) * e, zb = ((M - 1) * ldz + 16) * e;
-  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31), "hcb.dense_conv3x3_wgrad: tensors must stay below 2 GiB (32-bit offsets)");
-  check_range(x, xb, "x");
-  check_range(dz, zb, "dz");
-  check_align16(x.data_ptr(), "x");
-  check_align16(dz.data_ptr(), "dz");
+  check_act_rows("dense_conv3x3_wgrad", x, xb, "x");
+  check_act_rows("dense_conv3x3_wgrad", dz, zb, "dz");
   check_cuda(dw, "dw");
   TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.dim() == 2 && dw.size(0) == 16 && dw.stride(1) == 1 &&
                   dw.size(1) >= 9 * C && dw.stride(0) >= 9 * C,
               "hcb.dense_conv3x3_wgrad: dw must be float32 [16][>= 9 * C_in] with contiguous rows of stride >= 9 * C_in");
   check_range(dw, (15 * dw.stride(0) + 9 * C) * 4, "dw");
-  check_cuda(ws, "ws");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= pl.ws_floats,
-              "hcb.dense_conv3x3_wgrad: the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ",
-              pl.ws_floats, " (dense_conv3x3_wgrad_ws)");
   hcb::DenseWgradParams p{};
+  p.ws = check_ws("dense_conv3x3_wgrad", ws, pl.ws_floats);
   p.x = x.data_ptr();
   p.dz = dz.data_ptr();
-  p.gamma = opt_f32(gamma, C, "gamma");
-  p.beta = opt_f32(beta, C, "beta");
-  p.mean = opt_f32(mean, C, "saved_mean");
-  p.invstd = opt_f32(invstd, C, "saved_invstd");
-  p.ws = ws.data_ptr<float>();
+  attach_saved_bn(p, C, gamma, beta, mean, invstd);
   p.dw = dw.data_ptr<float>();
   p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldz = (int)ldz;
   p.Nout = (int)Nout; p.ldw = (int)dw.stride(0);
@@ -1890,28 +1879,18 @@ void preact_conv3x3_wgrad(const Tensor& x, const Tensor& dz, const Tensor& gamma
               "hcb.preact_conv3x3_wgrad: non-contiguous rows (channel stride must be 1, pixel stride ld)");
   const int64_t M = N * H * W, Mz = N * pl.P * pl.Q;
   const int64_t xb = ((M - 1) * ldx + C) * e, zb = ((Mz - 1) * ldz + Nout) * e;
-  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31), "hcb.preact_conv3x3_wgrad: tensors must stay below 2 GiB (32-bit offsets)");
-  check_range(x, xb, "x");
-  check_range(dz, zb, "dz");
-  check_align16(x.data_ptr(), "x");
-  check_align16(dz.data_ptr(), "dz");
+  check_act_rows("preact_conv3x3_wgrad", x, xb, "x");
+  check_act_rows("preact_conv3x3_wgrad", dz, zb, "dz");
   check_cuda(dw, "dw");
   TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.dim() == 2 && dw.size(0) == Nout && dw.stride(1) == 1 &&
                   dw.size(1) >= 9 * C && dw.stride(0) >= 9 * C,
               "hcb.preact_conv3x3_wgrad: dw must be float32 [Nout][>= 9 * C_in] with contiguous rows of stride >= 9 * C_in");
   check_range(dw, ((Nout - 1) * dw.stride(0) + 9 * C) * 4, "dw");
-  check_cuda(ws, "ws");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= pl.ws_floats,
-              "hcb.preact_conv3x3_wgrad: the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ",
-              pl.ws_floats, " (preact_conv3x3_wgrad_ws)");
   hcb::PreactWgradParams p{};
+  p.ws = check_ws("preact_conv3x3_wgrad", ws, pl.ws_floats);
   p.x = x.data_ptr();
   p.dz = dz.data_ptr();
-  p.gamma = opt_f32(gamma, C, "gamma");
-  p.beta = opt_f32(beta, C, "beta");
-  p.mean = opt_f32(mean, C, "saved_mean");
-  p.invstd = opt_f32(invstd, C, "saved_invstd");
-  p.ws = ws.data_ptr<float>();
+  attach_saved_bn(p, C, gamma, beta, mean, invstd);
   p.dw = dw.data_ptr<float>();
   p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldz = (int)ldz;
   p.Nout = (int)Nout; p.ldw = (int)dw.stride(0); p.stride = (int)g[7];
@@ -1960,14 +1939,9 @@ void dense_conv3x3_dgrad(const Tensor& x, const Tensor& dz, const Tensor& gin, c
               "hcb.dense_conv3x3_dgrad: non-contiguous rows (channel stride must be 1)");
   const int64_t M = N * H * W;
   const int64_t xb = ((M - 1) * ldx + C) * e, zb = ((M - 1) * ldz + 16) * e, gb = ((M - 1) * ldg + C) * e;
-  TORCH_CHECK(xb < (1ll << 31) && zb < (1ll << 31) && gb < (1ll << 31),
-              "hcb.dense_conv3x3_dgrad: tensors must stay below 2 GiB (32-bit offsets)");
-  check_range(x, xb, "x");
-  check_range(dz, zb, "dz");
-  check_range(gin, gb, "gin");
-  check_align16(x.data_ptr(), "x");
-  check_align16(dz.data_ptr(), "dz");
-  check_align16(gin.data_ptr(), "gin");
+  check_act_rows("dense_conv3x3_dgrad", x, xb, "x");
+  check_act_rows("dense_conv3x3_dgrad", dz, zb, "dz");
+  check_act_rows("dense_conv3x3_dgrad", gin, gb, "gin");
   // gin is updated while other workgroups still read halo pixels of dz: where the two views interleave (one
   // gradient buffer), the slot's 16 columns must lie beyond gin's C columns of the same rows
   const char *xp = (const char*)x.data_ptr(), *zp = (const char*)dz.data_ptr(), *gp = (const char*)gin.data_ptr();
@@ -1980,10 +1954,7 @@ void dense_conv3x3_dgrad(const Tensor& x, const Tensor& dz, const Tensor& gin, c
   check_f32(w, "w");
   TORCH_CHECK(w.is_contiguous() && w.dim() >= 2 && w.size(0) >= Nout && w.numel() == w.size(0) * 9 * C,
               "hcb.dense_conv3x3_dgrad: w must be the contiguous float32 kernel [>= Nout][3][3][C_in]");
-  check_cuda(ws, "ws");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= pl.ws_floats,
-              "hcb.dense_conv3x3_dgrad: the workspace holds ", ws.numel(), " floats (float32, contiguous), this problem needs ",
-              pl.ws_floats, " (dense_conv3x3_dgrad_ws)");
+  float* wsp = check_ws("dense_conv3x3_dgrad", ws, pl.ws_floats);
   check_f32(dgamma, "dgamma");
   check_f32(dbeta, "dbeta");
   TORCH_CHECK(dgamma.is_contiguous() && dbeta.is_contiguous() && dgamma.numel() >= C && dbeta.numel() >= C,
@@ -1993,11 +1964,8 @@ void dense_conv3x3_dgrad(const Tensor& x, const Tensor& dz, const Tensor& gin, c
   p.dz = dz.data_ptr();
   p.gin = gin.data_ptr();
   p.w = w.data_ptr<float>();
-  p.gamma = opt_f32(gamma, C, "gamma");
-  p.beta = opt_f32(beta, C, "beta");
-  p.mean = opt_f32(mean, C, "saved_mean");
-  p.invstd = opt_f32(invstd, C, "saved_invstd");
-  p.ws = ws.data_ptr<float>();
+  attach_saved_bn(p, C, gamma, beta, mean, invstd);
+  p.ws = wsp;
   p.dgamma = dgamma.data_ptr<float>();
   p.dbeta = dbeta.data_ptr<float>();
   p.N = (int)N; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.ldx = (int)ldx; p.ldz = (int)ldz; p.ldg = (int)ldg;

@@ -5,6 +5,9 @@
 // columns (12 padded to 16): it is bound by reading its input, and the unfused chain (BN apply writes
 // the operand, the GEMM reads it back, nine taps through L2) moves that input three times.
 //
+// The LDS unit and swizzle, the BN + ReLU patch store, the MFMA order, the coefficients from the replica sums
+// and the output-statistics reduction are the family's: patch3x3.h states them once.
+//
 // Work split (not a row of gemm_cfg.h): a workgroup of 4 waves owns a strip of TR whole output rows
 // of one image (TR * W <= 128 pixels = 8 MFMA tiles of 16 pixels, two per wave) and all 16 output
 // channels. It walks C in chunks of 32 channels, one MFMA K:
@@ -12,29 +15,23 @@
 //                         buffer loads; pixels outside the image and channels past C get the
 //                         out-of-range offset. The chunk's weights, 9 taps x 16 rows x 32 channels of
 //                         the [Nout][Kpad] pack (rows past Nout out of range: zeros), come the same way.
-//   registers -> LDS      BN + ReLU in fp32 (halo pixels are SELECTED to zero: the conv pads the
-//                         normalised map), then the MFMA operand: 16-bit, or on the fp32 path the
-//                         bf16 hi / mid / lo split into three tiles. LDS unit = 64 bytes (32 channels
-//                         of one pixel or weight row); its four 16-byte columns are XOR-swizzled with
-//                         bits 2..3 of the unit index, so the 16 lanes of a fragment read (16
-//                         consecutive units, one column) hit 16 distinct 16-byte bank groups.
-//   LDS -> MFMA           v_mfma_f32_16x16x32 (bf16, or f16 in the HCB_F16 build): A = the tap's weight
-//                         rows, B = 16 pixels, so a lane ends with 4 consecutive output channels of
-//                         one pixel (an 8- or 16-byte store). The nine taps read the resident patch:
-//                         an input element crosses global -> LDS once per layer. fp32: six products
-//                         per fragment pair, small terms first, as conv_p3 orders them.
+//   registers -> LDS      bnrelu_store (halo pixels are SELECTED to zero: the conv pads the normalised map).
+//   LDS -> MFMA           A = the tap's weight rows, B = 16 pixels, so a lane ends with 4 consecutive output
+//                         channels of one pixel (an 8- or 16-byte store). The nine taps read the resident
+//                         patch: an input element crosses global -> LDS once per layer.
 // Both LDS buffers (patch + weights) are doubled: the loads of chunk c + 1 are issued before the MFMAs
 // of chunk c and transformed and stored after them; one barrier per chunk. LDS-DMA is not usable here,
 // the data is transformed on its way.
 //
-// mean / invstd are finalised inside the kernel from the R replicas of the buffer's statistics
-// accumulator (sum(v - K), sum((v - K)^2), K the shift), as bn_apply_acc does; block 0 publishes them
-// and updates the moving statistics. The conv's own output statistics (of the fp32 accumulators, shifted)
-// are summed over the block's strips in registers, across lanes by shuffles, across waves through LDS in
-// wave order, and added once per block into replica blockIdx.x % R of the slot's columns. Deterministic
-// mode caps the grid at R blocks (the kernel strides over the strips), so every slot gets one add.
-// Output channels Nout..15 are stored as literal zeros, whatever the operands hold (an Inf or NaN input
-// cannot reach them), and their statistics stay zero.
+// This is preact3x3.hip's kernel at one column tile and stride 1, plus three things a slot of Nout <= 16 channels
+// needs: weight rows past Nout are read out of range, output channels Nout..15 are stored as literal zeros, whatever
+// the operands hold (an Inf or NaN input cannot reach them; their statistics stay zero), and stats_shift is read
+// only below Nout. Running it AS that kernel (stride and patch width as run-time parameters) was measured 1.1 - 3.7 %
+// slower on every layer shape (profiles/patch3x3_refactor.txt), so the two stay separate kernels over one set of
+// helpers; per output pixel both sum K in the same order, and y is bitwise equal between them.
+//
+// Block 0 publishes mean / invstd and updates the moving statistics. Deterministic mode caps the grid at R blocks
+// (the kernel strides over the strips), so every replica slot of the output statistics gets one add.
 //
 // Resources (hipcc -O3, gfx950; no scratch in either build or form):
 //   16-bit: 159 VGPRs (bf16 and fp16 builds), dynamic LDS = 8 * C32 + 512 + 2 * (patch_pix + 144) * 64 bytes
@@ -49,6 +46,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "patch3x3.h"
 
 namespace hcb {
 
@@ -60,11 +58,6 @@ constexpr int DN_TILES = 2;   // 16-pixel MFMA tiles per wave
 constexpr int DN_WUNITS = 9 * 16;
 constexpr uint32_t DN_WBYTES = DN_WUNITS * 64u;
 constexpr size_t DN_LDS_MAX = 160 * 1024;
-
-// byte offset of 16-byte column v of 64-byte unit `unit` (see the header)
-__device__ __forceinline__ uint32_t dn_off(int unit, int v) {
-  return (uint32_t)unit * 64u + (uint32_t)((v ^ ((unit >> 2) & 3)) << 4);
-}
 
 size_t dn_lds_bytes(int C, int patch_pix, bool f32) {
   const int Cr = (C + 31) & ~31;
@@ -85,41 +78,9 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
   char* bufs = smem + (size_t)(2 * Cr + 128) * 4;
   const uint32_t patch_b = (uint32_t)p.patch_pix * 64u;
   const uint32_t buf_b = NPL * (patch_b + DN_WBYTES);
-  const int M = p.N * p.H * p.W;
 
-  // ---- BN coefficients of the C input channels from the replica sums (bn_coef_fwd's arithmetic)
-  {
-    const float inv_n = 1.f / (float)M;
-    const bool pub = blockIdx.x == 0;
-    for (int c = tid; c < Cr; c += 256) {
-      float sc = 0.f, sh = 0.f;
-      if (c < p.C) {
-        float s = 0.f, q = 0.f;
-        for (int r = 0; r < p.R; ++r) {
-          s += p.acc[(size_t)r * 2 * p.acc_C + c];
-          q += p.acc[(size_t)r * 2 * p.acc_C + p.acc_C + c];
-        }
-        const float k = p.shift != nullptr ? p.shift[c] : 0.f;
-        const float d = s * inv_n;
-        const float mu = d + k;
-        const float var = fmaxf(q * inv_n - d * d, 0.f);
-        const float is = rsqrtf(var + p.eps);
-        sc = p.gamma[c] * is;
-        sh = p.beta[c] - mu * sc;
-        if (pub) {
-          if (p.saved_mean != nullptr) p.saved_mean[c] = mu;
-          if (p.saved_invstd != nullptr) p.saved_invstd[c] = is;
-          if (p.run_mean != nullptr) {
-            const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
-            p.run_mean[c] = p.momentum * p.run_mean[c] + (1.f - p.momentum) * mu;
-            p.run_var[c] = p.momentum * p.run_var[c] + (1.f - p.momentum) * unb;
-          }
-        }
-      }
-      coef[c] = sc;
-      coef[Cr + c] = sh;
-    }
-  }
+  // ---- BN coefficients of the C input channels from the replica sums; block 0 publishes the moments
+  bn_coef_from_acc(p, coef, Cr, p.N * p.H * p.W, blockIdx.x == 0);
   __syncthreads();
 
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x, p.x_bytes);
@@ -140,9 +101,9 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
     const int tap = unit >> 4, row = unit & 15;
     const bool ok = unit < DN_WUNITS && row < p.Nout;
     woff[it] = ok ? (uint32_t)(row * p.Kpad + tap * p.C) * 2u : HCB_OOB;
-    wlds[it] = unit < DN_WUNITS ? dn_off(unit, v) : HCB_OOB;
+    wlds[it] = unit < DN_WUNITS ? patch_off(unit, v) : HCB_OOB;
   }
-  const uint32_t a0 = dn_off(frow, fq);  // this lane's weight fragment of tap 0; tap t: + t * 1024
+  const uint32_t a0 = patch_off(frow, fq);  // this lane's weight fragment of tap 0; tap t: + t * 1024
 
   float kout[4];
 #pragma unroll
@@ -168,7 +129,7 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
       const bool in = pp < p.patch_pix;
       const bool ok = in && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
       goff[it] = ok ? (uint32_t)(((size_t)(n * p.H + h) * p.W + w) * p.ldx) * E : HCB_OOB;
-      plds[it] = in ? dn_off(pp, v) : HCB_OOB;
+      plds[it] = in ? patch_off(pp, v) : HCB_OOB;
     }
     // the pixel fragments this lane reads: tile = wave + 4 * ti, pixel frow of it (clamped into the strip)
     uint32_t baddr[DN_TILES][9];
@@ -177,7 +138,7 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
       const int o = min((wave + 4 * ti) * 16 + frow, npix - 1);
       const int orow = o / p.W, ocol = o - orow * p.W;
 #pragma unroll
-      for (int tap = 0; tap < 9; ++tap) baddr[ti][tap] = dn_off((orow + tap / 3) * W2 + ocol + tap % 3, fq);
+      for (int tap = 0; tap < 9; ++tap) baddr[ti][tap] = patch_off((orow + tap / 3) * W2 + ocol + tap % 3, fq);
     }
 
     Act8<T> xv[DN_MAXIT];
@@ -198,38 +159,10 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
       char* pb = bufs + (size_t)b * buf_b;
       char* wb = pb + NPL * patch_b;
       float sc[8], sh[8];
-      const f32x4* cs = reinterpret_cast<const f32x4*>(coef + c0 + v * 8);
-      const f32x4* ch = reinterpret_cast<const f32x4*>(coef + Cr + c0 + v * 8);
+      bn_coef_load8(coef, Cr, c0 + v * 8, sc, sh);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sc[e] = cs[0][e];
-        sc[4 + e] = cs[1][e];
-        sh[e] = ch[0][e];
-        sh[4 + e] = ch[1][e];
-      }
-#pragma unroll
-      for (int it = 0; it < DN_MAXIT; ++it) {
-        if (plds[it] == HCB_OOB) continue;
-        float f[8];
-        xv[it].to_f(f);
-        const bool ok = goff[it] != HCB_OOB;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = ok ? fmaxf(f[e] * sc[e] + sh[e], 0.f) : 0.f;
-        if constexpr (F32) {
-          u32x4 a, bq, hi, mid, lo;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            a[e] = __float_as_uint(f[e]);
-            bq[e] = __float_as_uint(f[4 + e]);
-          }
-          split3_8(a, bq, hi, mid, lo);
-          *reinterpret_cast<u32x4*>(pb + plds[it]) = hi;
-          *reinterpret_cast<u32x4*>(pb + patch_b + plds[it]) = mid;
-          *reinterpret_cast<u32x4*>(pb + 2 * patch_b + plds[it]) = lo;
-        } else {
-          *reinterpret_cast<u32x4*>(pb + plds[it]) = pack8(f);
-        }
-      }
+      for (int it = 0; it < DN_MAXIT; ++it)
+        if (plds[it] != HCB_OOB) bnrelu_store<T>(pb, patch_b, plds[it], xv[it], goff[it] != HCB_OOB, sc, sh);
 #pragma unroll
       for (int it = 0; it < DN_WIT; ++it) {
         if (wlds[it] == HCB_OOB) continue;
@@ -262,16 +195,7 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
             u32x4 bb[NPL];
 #pragma unroll
             for (int t = 0; t < NPL; ++t) bb[t] = *reinterpret_cast<const u32x4*>(pb + t * patch_b + baddr[ti][tap]);
-            if constexpr (F32) {
-              acc[ti] = mfma_bf16(a[2], bb[0], acc[ti]);
-              acc[ti] = mfma_bf16(a[0], bb[2], acc[ti]);
-              acc[ti] = mfma_bf16(a[1], bb[1], acc[ti]);
-              acc[ti] = mfma_bf16(a[1], bb[0], acc[ti]);
-              acc[ti] = mfma_bf16(a[0], bb[1], acc[ti]);
-              acc[ti] = mfma_bf16(a[0], bb[0], acc[ti]);
-            } else {
-              acc[ti] = mfma16(__builtin_bit_cast(act16x8, a[0]), __builtin_bit_cast(act16x8, bb[0]), acc[ti]);
-            }
+            mfma_acc<F32>(a, bb, acc[ti]);
           }
         }
       }
@@ -311,25 +235,7 @@ __global__ __launch_bounds__(256) void dense_conv3x3_kernel(DenseParams p) {
   }
 
   if (p.stats == nullptr) return;  // (uniform)
-  // lanes of one fq hold the same 4 channels: sum the 16 pixels, then the 4 waves in wave order
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      s1[e] += __shfl_xor(s1[e], o, 64);
-      s2[e] += __shfl_xor(s2[e], o, 64);
-    }
-    if (frow == 0) {
-      red[wave * 32 + fq * 4 + e] = s1[e];
-      red[wave * 32 + 16 + fq * 4 + e] = s2[e];
-    }
-  }
-  __syncthreads();
-  if (tid < 32) {
-    const float a = red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid];
-    float* dst = p.stats + (size_t)(blockIdx.x % p.stats_R) * 2 * p.stats_C;
-    atomicAdd(dst + (tid < 16 ? tid : p.stats_C + tid - 16), a);
-  }
+  stats_reduce<1>(s1, s2, red, p.stats, p.stats_R, p.stats_C, 0, wave, frow, fq);
 }
 
 // strip rows and patch size for this problem; false when even one-row strips do not fit
@@ -358,21 +264,6 @@ bool dn_plan(int H, int W, int C, bool f32, int* TR_out, int* pix_out, size_t* l
   return false;
 }
 
-template <typename T>
-void dn_launch(const DenseParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  // more than the default 64 KiB of dynamic LDS: raised on every launch (a host-side attribute of the
-  // current device's function, no stream work), so every device gets it and a failure is seen here
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)dense_conv3x3_kernel<T>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_LDS_MAX);
-    if (e != hipSuccess) {
-      fprintf(stderr, "hcb dense_conv3x3: cannot raise the dynamic LDS limit: %s\n", hipGetErrorString(e));
-      abort();
-    }
-  }
-  hipLaunchKernelGGL((dense_conv3x3_kernel<T>), grid, dim3(256), lds, st, p);
-}
-
 }  // namespace
 
 bool dense_conv3x3_fits(int N, int H, int W, int C, bool f32) {
@@ -394,9 +285,9 @@ void launch_dense_conv3x3(const DenseParams& p0, hipStream_t st, bool f32) {
   // deterministic mode: at most R blocks, so each replica slot receives a single add
   if (p.stats != nullptr && deterministic() && (int)grid.x > p.stats_R) grid.x = p.stats_R;
   if (f32)
-    dn_launch<float>(p, grid, lds, st);
+    launch_big_lds(dense_conv3x3_kernel<float>, grid, lds, st, p, "dense_conv3x3");
   else
-    dn_launch<uint16_t>(p, grid, lds, st);
+    launch_big_lds(dense_conv3x3_kernel<uint16_t>, grid, lds, st, p, "dense_conv3x3");
 }
 
 }  // namespace hcb

@@ -32,7 +32,7 @@
 //             lane's 16-byte read goes to the address of ITS pixel shifted by ITS tap inside the patch, so the
 //             row wrap of the strip inside the (W + 2)-wide patch is absorbed by the per-lane address. A lane
 //             ends with 4 consecutive channels of one pixel, the forward kernel's store shape. fp32: six
-//             products per fragment pair, small terms first, as conv_p3 orders them.
+//             products per fragment pair, small terms first (patch3x3.h: mfma_acc, shared with the family).
 //   epilogue  x (and gin on APPLY) of the lane's 4 channels x 4 tiles are loaded straight into registers
 //             before the MFMAs (8 or 16 bytes per access; the 4 lanes of a pixel cover 32 or 64 contiguous
 //             bytes per half); sc, sh, mean, invstd of the lane's 8 channels live in registers.
@@ -66,6 +66,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "patch3x3.h"
 
 namespace hcb {
 
@@ -301,16 +302,7 @@ __global__ __launch_bounds__(256) void dense_dgrad_kernel(DenseDgradParams p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           if (!(h == 0 ? live0 : live1)) continue;
-          if constexpr (F32) {
-            acc[ti][h] = mfma_bf16(a[h][2], bb[0], acc[ti][h]);
-            acc[ti][h] = mfma_bf16(a[h][0], bb[2], acc[ti][h]);
-            acc[ti][h] = mfma_bf16(a[h][1], bb[1], acc[ti][h]);
-            acc[ti][h] = mfma_bf16(a[h][1], bb[0], acc[ti][h]);
-            acc[ti][h] = mfma_bf16(a[h][0], bb[1], acc[ti][h]);
-            acc[ti][h] = mfma_bf16(a[h][0], bb[0], acc[ti][h]);
-          } else {
-            acc[ti][h] = mfma16(__builtin_bit_cast(act16x8, a[h][0]), __builtin_bit_cast(act16x8, bb[0]), acc[ti][h]);
-          }
+          mfma_acc<F32>(a[h], bb, acc[ti][h]);
         }
       }
     }
@@ -403,16 +395,7 @@ __global__ __launch_bounds__(256) void dense_dgrad_fold_kernel(DenseDgradParams 
 
 template <typename T, bool APPLY>
 void dg_launch(const DenseDgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  // more than the default 64 KiB of dynamic LDS: raised on every launch, as dense3x3.hip does
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)dense_dgrad_kernel<T, APPLY>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)DG_LDS_MAX);
-    if (e != hipSuccess) {
-      fprintf(stderr, "hcb dense_conv3x3_dgrad: cannot raise the dynamic LDS limit: %s\n", hipGetErrorString(e));
-      abort();
-    }
-  }
-  hipLaunchKernelGGL((dense_dgrad_kernel<T, APPLY>), grid, dim3(256), lds, st, p);
+  launch_big_lds(dense_dgrad_kernel<T, APPLY>, grid, lds, st, p, "dense_conv3x3_dgrad");
 }
 
 }  // namespace

@@ -16,9 +16,8 @@
 //   registers -> LDS      BN + ReLU in fp32 in the forward's fmaxf(f * sc + sh, 0.f) form (the thread's 8
 //                         channels never change: their sc / sh live in registers), halo pixels SELECTED
 //                         to zero; then 16-bit, or on the fp32 path the bf16 hi / mid / lo split into
-//                         three tiles. dz takes the same split in registers. Patch unit = 64 bytes (32
-//                         channels of one pixel), 16-byte columns XOR-swizzled as in dense3x3.hip; dz
-//                         rows are 32 bytes (16 channels of one pixel), unswizzled.
+//                         three tiles (patch3x3.h: the shared unit, swizzle and patch store). dz takes the
+//                         same split in registers; dz rows are 32 bytes (16 channels of one pixel), unswizzled.
 //   LDS -> MFMA           v_mfma_f32_16x16x32 (bf16, or f16 in the HCB_F16 build) with the PIXEL index as
 //                         K: A = 16 dz channels, B = 16 input channels. Both operands are pixel-major in
 //                         LDS and are read K-major with the transposed read ds_read_b64_tr_b16: a lane
@@ -37,7 +36,7 @@
 //
 // After its slab the workgroup adds the kh = 1 waves' tiles to the kh = 0 waves' through LDS (fixed
 // order) and stores the chunk's [16][9][32] partial into the caller's workspace [slabs][16][9][C32].
-// dense_wgrad_fold_kernel then sums the slabs in a fixed order (16 interleaved slab sequences per element,
+// wgrad_fold_kernel (patch3x3.h) then sums the slabs in a fixed order (16 interleaved slab sequences per element,
 // each in slab order, added in sequence order) and does the single dw += per element of
 // rows 0 .. Nout - 1; rows Nout..15 receive nothing. No atomics, no memset, no reliance on zeroed memory:
 // every workspace element that is read was written by the launch before. The result is bitwise
@@ -48,7 +47,7 @@
 // Resources (hipcc -O3, gfx950; no scratch in either build or form):
 //   16-bit: 90 VGPRs + 36 AGPRs (bf16 and fp16 builds), dynamic LDS = 2 * (patch_pix * 64 + 4096) bytes (>= 18 KiB)
 //   fp32:   136 VGPRs + 36 AGPRs (both builds), dynamic LDS = 6 * (patch_pix * 64 + 4096) bytes (three tiles of each)
-//   fold:   12 VGPRs, 1 KiB of static LDS
+//   fold:   14 VGPRs, 1088 bytes of static LDS (the shared wgrad_fold_kernel)
 // with patch_pix = (TR + 2) * (W + 2) <= 320 and TR = min(128 / W, 16, H) (8 x 8 maps: whole images, so that
 // all four waves have a K block; 16 x 16: 8 rows; 32 x 32: 4 rows, 34 KiB / 101 KiB).
 #include <cstdio>
@@ -56,6 +55,8 @@
 
 #include "common.h"
 #include "kernels.h"
+#define PATCH3X3_WGRAD_FOLD
+#include "patch3x3.h"
 
 namespace hcb {
 
@@ -67,19 +68,6 @@ constexpr uint32_t DW_DZB = DW_STRIP * 32u;
 constexpr uint32_t DW_RED_BYTES = 18 * 64 * 16;  // the kh = 1 waves' tiles on their way to the kh = 0 waves
 constexpr size_t DW_LDS_MAX = 160 * 1024;
 constexpr int DW_TARGET_WGS = 256;
-
-// byte offset of 16-byte column v of 64-byte patch unit `unit` (dense3x3.hip's swizzle)
-__device__ __forceinline__ uint32_t dw_off(int unit, int v) {
-  return (uint32_t)unit * 64u + (uint32_t)((v ^ ((unit >> 2) & 3)) << 4);
-}
-
-// 8 K values of one fragment column: two transposed reads of 4 pixels each
-__device__ __forceinline__ u32x4 dw_frag(const char* r0, const char* r1) {
-  const short4v a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v HCB_LDS*)r0);
-  const short4v b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v HCB_LDS*)r1);
-  const short8 t = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(u32x4, t);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void dense_wgrad_kernel(DenseWgradParams p) {
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(DenseWgradParams p) {
     const bool ok = in && cok && (unsigned)(c - 1) < (unsigned)p.W;
     prow[it] = ok ? r - 1 : -0x10000;  // (far outside every image)
     poff[it] = (((r - 1) * p.W + c - 1) * p.ldx + cc) * (int)E;
-    plds[it] = in ? dw_off(pp, v) : HCB_OOB;
+    plds[it] = in ? patch_off(pp, v) : HCB_OOB;
   }
   // the dz vector this thread stages: pixel tid >> 1 of the strip, channels 8 * (tid & 1) .. + 7
   const int zpix = tid >> 1;
@@ -164,28 +152,8 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(DenseWgradParams p) {
     char* pb = smem + (size_t)b * buf_b;
     char* zb = pb + NPL * patch_b;
 #pragma unroll
-    for (int it = 0; it < DW_MAXIT; ++it) {
-      if (plds[it] == HCB_OOB) continue;
-      float f[8];
-      xv[it].to_f(f);
-      const bool ok = (okmask >> it) & 1u;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = ok ? fmaxf(f[e] * sc[e] + sh[e], 0.f) : 0.f;
-      if constexpr (F32) {
-        u32x4 a, bq, hi, mid, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          a[e] = __float_as_uint(f[e]);
-          bq[e] = __float_as_uint(f[4 + e]);
-        }
-        split3_8(a, bq, hi, mid, lo);
-        *reinterpret_cast<u32x4*>(pb + plds[it]) = hi;
-        *reinterpret_cast<u32x4*>(pb + patch_b + plds[it]) = mid;
-        *reinterpret_cast<u32x4*>(pb + 2 * patch_b + plds[it]) = lo;
-      } else {
-        *reinterpret_cast<u32x4*>(pb + plds[it]) = pack8(f);
-      }
-    }
+    for (int it = 0; it < DW_MAXIT; ++it)
+      if (plds[it] != HCB_OOB) bnrelu_store<T>(pb, patch_b, plds[it], xv[it], (okmask >> it) & 1u, sc, sh);
     if constexpr (F32) {
       u32x4 hi, mid, lo;
       split3_8(zv.a, zv.b, hi, mid, lo);
@@ -220,7 +188,7 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(DenseWgradParams p) {
 #pragma unroll
         for (int t = 0; t < NPL; ++t) {
           const char* ap = zb + t * DW_DZB + kb * 1024 + aaddr;
-          a[t] = dw_frag(ap, ap + 128);
+          a[t] = frag_tr16(ap, ap + 128);
         }
         // the patch units of this lane's two pixels at tap (0, 0); pixels past the strip clamp into it
         int unit[2];
@@ -233,20 +201,11 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(DenseWgradParams p) {
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
           const int d = (tap / 3) * W2 + tap % 3;
-          const uint32_t o0 = dw_off(unit[0] + d, bcol) + bsub, o1 = dw_off(unit[1] + d, bcol) + bsub;
+          const uint32_t o0 = patch_off(unit[0] + d, bcol) + bsub, o1 = patch_off(unit[1] + d, bcol) + bsub;
           u32x4 bb[NPL];
 #pragma unroll
-          for (int t = 0; t < NPL; ++t) bb[t] = dw_frag(pb + t * patch_b + o0, pb + t * patch_b + o1);
-          if constexpr (F32) {
-            acc[tap] = mfma_bf16(a[2], bb[0], acc[tap]);
-            acc[tap] = mfma_bf16(a[0], bb[2], acc[tap]);
-            acc[tap] = mfma_bf16(a[1], bb[1], acc[tap]);
-            acc[tap] = mfma_bf16(a[1], bb[0], acc[tap]);
-            acc[tap] = mfma_bf16(a[0], bb[1], acc[tap]);
-            acc[tap] = mfma_bf16(a[0], bb[0], acc[tap]);
-          } else {
-            acc[tap] = mfma16(__builtin_bit_cast(act16x8, a[0]), __builtin_bit_cast(act16x8, bb[0]), acc[tap]);
-          }
+          for (int t = 0; t < NPL; ++t) bb[t] = frag_tr16(pb + t * patch_b + o0, pb + t * patch_b + o1);
+          mfma_acc<F32>(a, bb, acc[tap]);
         }
       }
     }
@@ -271,47 +230,6 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(DenseWgradParams p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) dst[((size_t)e * 9 + tap) * C32] = acc[tap][e] + o[e];
   }
-}
-
-// dw[n][tap * C + c] += sum over the slabs of ws[slab][n][tap][c]; rows n < Nout only. A block folds 16
-// consecutive elements: thread (sl, el) sums slabs sl, sl + 16, ... of element el in slab order, then the 16
-// partial sums meet in LDS and are added in sl order -- a fixed order, whatever the device
-__global__ __launch_bounds__(256) void dense_wgrad_fold_kernel(DenseWgradParams p) {
-  __shared__ float part[16][17];
-  const int el = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + el;
-  const int K = 9 * p.C;
-  const bool ok = idx < p.Nout * K;
-  const int n = ok ? idx / K : 0, k = ok ? idx - n * K : 0;
-  float s = 0.f;
-  if (ok) {
-    const int tap = k / p.C, c = k - tap * p.C;
-    const int C32 = (p.C + 31) & ~31;
-    const size_t stride = (size_t)16 * 9 * C32;
-    const float* src = p.ws + ((size_t)n * 9 + tap) * C32 + c;
-    for (int b = sl; b < p.nslabs; b += 16) s += src[b * stride];
-  }
-  part[sl][el] = s;
-  __syncthreads();
-  if (sl != 0 || !ok) return;
-  float t = part[0][el];
-#pragma unroll
-  for (int j = 1; j < 16; ++j) t += part[j][el];
-  p.dw[(size_t)n * p.ldw + k] += t;
-}
-
-template <typename T>
-void dw_launch(const DenseWgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  // more than the default 64 KiB of dynamic LDS: raised on every launch, as dense3x3.hip does
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)dense_wgrad_kernel<T>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_LDS_MAX);
-    if (e != hipSuccess) {
-      fprintf(stderr, "hcb dense_conv3x3_wgrad: cannot raise the dynamic LDS limit: %s\n", hipGetErrorString(e));
-      abort();
-    }
-  }
-  hipLaunchKernelGGL((dense_wgrad_kernel<T>), grid, dim3(256), lds, st, p);
 }
 
 }  // namespace
@@ -362,11 +280,13 @@ void launch_dense_conv3x3_wgrad(const DenseWgradParams& p0, hipStream_t st, bool
   p.nslabs = pl.nslabs;
   const dim3 grid((unsigned)(((p.C + 31) / 32) * pl.nslabs));
   if (f32)
-    dw_launch<float>(p, grid, pl.lds_bytes, st);
+    launch_big_lds(dense_wgrad_kernel<float>, grid, pl.lds_bytes, st, p, "dense_conv3x3_wgrad");
   else
-    dw_launch<uint16_t>(p, grid, pl.lds_bytes, st);
+    launch_big_lds(dense_wgrad_kernel<uint16_t>, grid, pl.lds_bytes, st, p, "dense_conv3x3_wgrad");
+  // the workspace has 16 rows per slab; rows Nout..15 of dw receive nothing
   const int total = p.Nout * 9 * p.C;
-  hipLaunchKernelGGL(dense_wgrad_fold_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(wgrad_fold_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, p.ws, p.dw, p.C, p.ldw,
+                     p.nslabs, 16, p.Nout);
 }
 
 }  // namespace hcb

@@ -24,11 +24,9 @@
 //                         loads: pixels outside the image and channels past C_in get the out-of-range
 //                         offset. The chunk's weights, 9 taps x the workgroup's output rows x 32 channels of
 //                         the [Nout][Kpad] pack (K = (tap, c): the ParamStore pack, or dense_pack's), likewise.
-//   registers -> LDS      BN + ReLU in fp32, halo selected to zero, then the MFMA operand: 16-bit, or on the
-//                         fp32 path the bf16 hi / mid / lo split into three tiles. LDS unit = 64 bytes (32
-//                         channels of one pixel or weight row); its four 16-byte columns are XOR-swizzled
-//                         with bits 2..3 of the unit index (stride 1: a fragment's 16 units are consecutive
-//                         and conflict-free; stride 2 reads every other unit: 2-way).
+//   registers -> LDS      the family's patch store, 64-byte LDS unit and swizzle (patch3x3.h states them once;
+//                         stride 1: a fragment's 16 units are consecutive and conflict-free; stride 2 reads
+//                         every other unit: 2-way).
 //   LDS -> MFMA           v_mfma_f32_16x16x32 (bf16, or f16 in the HCB_F16 build): A = the tap's 16 weight
 //                         rows of the wave's column tile (read once per tap, used for both pixel tiles),
 //                         B = 16 output pixels read from the resident patch at pixel (orow s + ty, ocol s +
@@ -54,6 +52,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "patch3x3.h"
 
 namespace hcb {
 
@@ -62,11 +61,6 @@ namespace {
 constexpr int PA_MAXIT = 5;  // patch vectors (8 channels of one pixel) per thread and chunk: patch_pix * 4 <= 5 * 256
 constexpr int PA_TILES = 2;  // 16-pixel MFMA tiles per wave
 constexpr size_t PA_LDS_MAX = 160 * 1024;
-
-// byte offset of 16-byte column v of 64-byte unit `unit` (see the header)
-__device__ __forceinline__ uint32_t pa_off(int unit, int v) {
-  return (uint32_t)unit * 64u + (uint32_t)((v ^ ((unit >> 2) & 3)) << 4);
-}
 
 // NCT: the column tiles (of 16 output channels) this workgroup computes, spread over its 4 waves
 template <typename T, int NCT>
@@ -92,40 +86,8 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
   const uint32_t buf_b = NPL * (patch_b + WBYTES);
   const int s = p.stride;
 
-  // ---- BN coefficients of the input channels from the replica sums (bn_coef_fwd's arithmetic)
-  {
-    const int M = p.N * p.H * p.W;
-    const float inv_n = 1.f / (float)M;
-    const bool pub = blockIdx.x == 0 && blockIdx.y == 0;
-    for (int c = tid; c < Cr; c += 256) {
-      float sc = 0.f, sh = 0.f;
-      if (c < p.C) {
-        float su = 0.f, q = 0.f;
-        for (int r = 0; r < p.R; ++r) {
-          su += p.acc[(size_t)r * 2 * p.acc_C + c];
-          q += p.acc[(size_t)r * 2 * p.acc_C + p.acc_C + c];
-        }
-        const float k = p.shift != nullptr ? p.shift[c] : 0.f;
-        const float d = su * inv_n;
-        const float mu = d + k;
-        const float var = fmaxf(q * inv_n - d * d, 0.f);
-        const float is = rsqrtf(var + p.eps);
-        sc = p.gamma[c] * is;
-        sh = p.beta[c] - mu * sc;
-        if (pub) {
-          if (p.saved_mean != nullptr) p.saved_mean[c] = mu;
-          if (p.saved_invstd != nullptr) p.saved_invstd[c] = is;
-          if (p.run_mean != nullptr) {
-            const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
-            p.run_mean[c] = p.momentum * p.run_mean[c] + (1.f - p.momentum) * mu;
-            p.run_var[c] = p.momentum * p.run_var[c] + (1.f - p.momentum) * unb;
-          }
-        }
-      }
-      coef[c] = sc;
-      coef[Cr + c] = sh;
-    }
-  }
+  // ---- BN coefficients of the input channels from the replica sums; block (0, 0) publishes the moments
+  bn_coef_from_acc(p, coef, Cr, p.N * p.H * p.W, blockIdx.x == 0 && blockIdx.y == 0);
   __syncthreads();
 
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x, p.x_bytes);
@@ -145,9 +107,9 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
     const int tap = unit / NW, row = unit - tap * NW;
     const bool ok = unit < WUNITS;
     woff[it] = ok ? (uint32_t)((n0 + row) * p.Kpad + tap * p.C) * 2u : HCB_OOB;
-    wlds[it] = ok ? pa_off(unit, v) : HCB_OOB;
+    wlds[it] = ok ? patch_off(unit, v) : HCB_OOB;
   }
-  const uint32_t a0 = pa_off(ct * 16 + frow, fq);  // this lane's weight fragment of tap 0; tap t: + t * NW * 64
+  const uint32_t a0 = patch_off(ct * 16 + frow, fq);  // this lane's weight fragment of tap 0; tap t: + t * NW * 64
 
   float kout[4];
 #pragma unroll
@@ -174,7 +136,7 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
       const bool in = pp < p.patch_pix;
       const bool ok = in && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
       goff[it] = ok ? (uint32_t)(((size_t)(n * p.H + h) * p.W + w) * p.ldx) * E : HCB_OOB;
-      plds[it] = in ? pa_off(pp, v) : HCB_OOB;
+      plds[it] = in ? patch_off(pp, v) : HCB_OOB;
     }
     // the pixel fragments this lane reads: tile = pw + NPW * ti, output pixel frow of it (clamped into the strip)
     uint32_t baddr[PA_TILES][9];
@@ -184,7 +146,7 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
       const int orow = o / p.Q, ocol = o - orow * p.Q;
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap)
-        baddr[ti][tap] = pa_off((orow * s + tap / 3) * p.PW + ocol * s + tap % 3, fq);
+        baddr[ti][tap] = patch_off((orow * s + tap / 3) * p.PW + ocol * s + tap % 3, fq);
     }
 
     Act8<T> xv[PA_MAXIT];
@@ -205,38 +167,10 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
       char* pb = bufs + (size_t)b * buf_b;
       char* wb = pb + NPL * patch_b;
       float sc[8], sh[8];
-      const f32x4* cs = reinterpret_cast<const f32x4*>(coef + c0 + v * 8);
-      const f32x4* ch = reinterpret_cast<const f32x4*>(coef + Cr + c0 + v * 8);
+      bn_coef_load8(coef, Cr, c0 + v * 8, sc, sh);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sc[e] = cs[0][e];
-        sc[4 + e] = cs[1][e];
-        sh[e] = ch[0][e];
-        sh[4 + e] = ch[1][e];
-      }
-#pragma unroll
-      for (int it = 0; it < PA_MAXIT; ++it) {
-        if (plds[it] == HCB_OOB) continue;
-        float f[8];
-        xv[it].to_f(f);
-        const bool ok = goff[it] != HCB_OOB;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = ok ? fmaxf(f[e] * sc[e] + sh[e], 0.f) : 0.f;
-        if constexpr (F32) {
-          u32x4 a, bq, hi, mid, lo;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            a[e] = __float_as_uint(f[e]);
-            bq[e] = __float_as_uint(f[4 + e]);
-          }
-          split3_8(a, bq, hi, mid, lo);
-          *reinterpret_cast<u32x4*>(pb + plds[it]) = hi;
-          *reinterpret_cast<u32x4*>(pb + patch_b + plds[it]) = mid;
-          *reinterpret_cast<u32x4*>(pb + 2 * patch_b + plds[it]) = lo;
-        } else {
-          *reinterpret_cast<u32x4*>(pb + plds[it]) = pack8(f);
-        }
-      }
+      for (int it = 0; it < PA_MAXIT; ++it)
+        if (plds[it] != HCB_OOB) bnrelu_store<T>(pb, patch_b, plds[it], xv[it], goff[it] != HCB_OOB, sc, sh);
 #pragma unroll
       for (int it = 0; it < WIT; ++it) {
         if (wlds[it] == HCB_OOB) continue;
@@ -269,16 +203,7 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
             u32x4 bb[NPL];
 #pragma unroll
             for (int t = 0; t < NPL; ++t) bb[t] = *reinterpret_cast<const u32x4*>(pb + t * patch_b + baddr[ti][tap]);
-            if constexpr (F32) {
-              acc[ti] = mfma_bf16(a[2], bb[0], acc[ti]);
-              acc[ti] = mfma_bf16(a[0], bb[2], acc[ti]);
-              acc[ti] = mfma_bf16(a[1], bb[1], acc[ti]);
-              acc[ti] = mfma_bf16(a[1], bb[0], acc[ti]);
-              acc[ti] = mfma_bf16(a[0], bb[1], acc[ti]);
-              acc[ti] = mfma_bf16(a[0], bb[0], acc[ti]);
-            } else {
-              acc[ti] = mfma16(__builtin_bit_cast(act16x8, a[0]), __builtin_bit_cast(act16x8, bb[0]), acc[ti]);
-            }
+            mfma_acc<F32>(a, bb, acc[ti]);
           }
         }
       }
@@ -313,41 +238,13 @@ __global__ __launch_bounds__(256) void preact_conv3x3_kernel(PreactParams p) {
   }
 
   if (p.stats == nullptr) return;  // (uniform)
-  // lanes of one fq hold the same 4 channels: sum the 16 pixels, then the waves of the column tile in wave order
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      s1[e] += __shfl_xor(s1[e], o, 64);
-      s2[e] += __shfl_xor(s2[e], o, 64);
-    }
-    if (frow == 0) {
-      red[wave * 32 + fq * 4 + e] = s1[e];
-      red[wave * 32 + 16 + fq * 4 + e] = s2[e];
-    }
-  }
-  __syncthreads();
-  if (tid < 32 * NCT) {
-    const int t = tid >> 5, j = tid & 31;  // column tile t (waves t, t + NCT, ...), sum j < 16, square sum j >= 16
-    float a = 0.f;
-#pragma unroll
-    for (int k = 0; k < NPW; ++k) a += red[(k * NCT + t) * 32 + j];
-    float* dst = p.stats + (size_t)(blockIdx.x % p.stats_R) * 2 * p.stats_C + n0 + t * 16;
-    atomicAdd(dst + (j < 16 ? j : p.stats_C + j - 16), a);
-  }
+  stats_reduce<NCT>(s1, s2, red, p.stats, p.stats_R, p.stats_C, n0, wave, frow, fq);
 }
 
 struct PaPlan {
   int nct, gy, TR, P, Q, pt, pl, PW, pix;
   size_t lds;
 };
-
-// TF 'SAME' for a 3-wide window: output size and the leading pad
-void pa_same(int size, int s, int* out, int* lead) {
-  *out = (size + s - 1) / s;
-  const int total = (*out - 1) * s + 3 - size;
-  *lead = (total > 0 ? total : 0) / 2;
-}
 
 // column tiles per workgroup, strip rows and patch size for this problem; false when it does not fit
 bool pa_plan(int H, int W, int C, int Nout, int s, bool f32, PaPlan* pl) {
@@ -356,8 +253,8 @@ bool pa_plan(int H, int W, int C, int Nout, int s, bool f32, PaPlan* pl) {
   const int nct_all = Nout / 16;
   pl->nct = f32 && nct_all > 2 ? 2 : nct_all;
   pl->gy = nct_all / pl->nct;
-  pa_same(H, s, &pl->P, &pl->pt);
-  pa_same(W, s, &pl->Q, &pl->pl);
+  same3(H, s, &pl->P, &pl->pt);
+  same3(W, s, &pl->Q, &pl->pl);
   const int maxpix = 16 * PA_TILES * (4 / pl->nct);
   const int Cr = (C + 31) & ~31;
   const int nbuf = Cr > 32 ? 2 : 1;
@@ -378,29 +275,15 @@ bool pa_plan(int H, int W, int C, int Nout, int s, bool f32, PaPlan* pl) {
   return false;
 }
 
-template <typename T, int NCT>
-void pa_launch(const PreactParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  // more than the default 64 KiB of dynamic LDS: raised on every launch (a host-side attribute of the
-  // current device's function, no stream work), so every device gets it and a failure is seen here
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)preact_conv3x3_kernel<T, NCT>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PA_LDS_MAX);
-    if (e != hipSuccess) {
-      fprintf(stderr, "hcb preact_conv3x3: cannot raise the dynamic LDS limit: %s\n", hipGetErrorString(e));
-      abort();
-    }
-  }
-  hipLaunchKernelGGL((preact_conv3x3_kernel<T, NCT>), grid, dim3(256), lds, st, p);
-}
-
 template <typename T>
 void pa_launch_t(const PreactParams& p, int nct, dim3 grid, size_t lds, hipStream_t st) {
+  const char* name = "preact_conv3x3";
   if (nct == 1)
-    pa_launch<T, 1>(p, grid, lds, st);
+    launch_big_lds(preact_conv3x3_kernel<T, 1>, grid, lds, st, p, name);
   else if (nct == 2)
-    pa_launch<T, 2>(p, grid, lds, st);
+    launch_big_lds(preact_conv3x3_kernel<T, 2>, grid, lds, st, p, name);
   else if constexpr (sizeof(T) == 2)  // (fp32 never has more than two column tiles per workgroup: pa_plan)
-    pa_launch<T, 4>(p, grid, lds, st);
+    launch_big_lds(preact_conv3x3_kernel<T, 4>, grid, lds, st, p, name);
 }
 
 }  // namespace

@@ -29,7 +29,7 @@
 //                         change: sc / sh live in registers), halo pixels SELECTED to zero, not normalised; then
 //                         16-bit, or on the fp32 path the bf16 hi / mid / lo split into three tiles, dz likewise.
 //                         Patch unit = 32 NH bytes per pixel, its 16-byte columns XOR-swizzled with bits 2.. of the unit
-//                         index (preact3x3.hip's swizzle); dz rows are 2 Nout bytes, their 32-byte tile columns
+//                         index (patch3x3.h: the shared unit, swizzle and patch store); dz rows are 2 Nout bytes, their 32-byte tile columns
 //                         XOR-swizzled with the pixel index.
 //   LDS -> MFMA           v_mfma_f32_16x16x32 (bf16, or f16 in the HCB_F16 build) with the OUTPUT PIXEL as K: A = 16
 //                         dz channels, B = 16 input channels. Both operands are pixel-major in LDS and are read K-major
@@ -42,7 +42,7 @@
 // shape) the plan single-buffers. LDS-DMA is not usable: the data changes on its way.
 //
 // After its slab the workgroup adds the K-split waves' tiles through LDS in kh order and stores the chunk's
-// [Nout][9][32] partial into the caller's workspace [slabs][Nout][9][C32]. preact_wgrad_fold_kernel sums the slabs in a
+// [Nout][9][32] partial into the caller's workspace [slabs][Nout][9][C32]. wgrad_fold_kernel (patch3x3.h) sums the slabs in a
 // fixed order and does the single dw += per element. No atomics, no memset, no reliance on zeroed memory: every
 // workspace element that is read was written by the launch before. Bitwise reproducible in every mode.
 // Slab rule (a function of the shape alone, not of the dtype or device): as many slabs as keep
@@ -65,6 +65,8 @@
 
 #include "common.h"
 #include "kernels.h"
+#define PATCH3X3_WGRAD_FOLD
+#include "patch3x3.h"
 
 namespace hcb {
 
@@ -74,20 +76,6 @@ constexpr int PW_MAXIT = 8;            // patch vectors (8 channels of one pixel
 constexpr int PW_STRIP = 128;          // output pixels of a strip at most
 constexpr size_t PW_LDS_MAX = 160 * 1024;
 constexpr int PW_TARGET_WGS = 256;
-
-// byte offset of 16-byte column v of patch unit `unit` (VPP columns of 16 bytes)
-template <int VPP>
-__device__ __forceinline__ uint32_t pw_off(int unit, int v) {
-  return (uint32_t)unit * (16u * VPP) + (uint32_t)((v ^ ((unit >> 2) & (VPP - 1))) << 4);
-}
-
-// 8 K values of one fragment column: two transposed reads of 4 pixels each
-__device__ __forceinline__ u32x4 pw_frag(const char* r0, const char* r1) {
-  const short4v a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v HCB_LDS*)r0);
-  const short4v b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v HCB_LDS*)r1);
-  const short8 t = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(u32x4, t);
-}
 
 // NRT: row tiles (16 dz channels each), NH: 16-channel halves of the chunk that exist
 template <typename T, int NRT, int NH>
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(256) void preact_wgrad_kernel(PreactWgradParams p) 
     const bool ok = in && (unsigned)(c - p.pl) < (unsigned)p.W;
     prow[it] = ok ? r : -0x10000;
     poff[it] = ((r * p.W + c - p.pl) * p.ldx + cc) * (int)E;
-    plds[it] = in ? pw_off<VPP>(pp, v) : HCB_OOB;
+    plds[it] = in ? patch_off<VPP>(pp, v) : HCB_OOB;
   }
   // the dz vectors this thread stages: pixel zp of the strip, channels 8 zv .. + 7
   int zpx[ZIT], zoff[ZIT];
@@ -196,25 +184,7 @@ __global__ __launch_bounds__(256) void preact_wgrad_kernel(PreactWgradParams p) 
 #pragma unroll
     for (int it = 0; it < PW_MAXIT; ++it) {
       if (it >= p.nit || plds[it] == HCB_OOB) continue;
-      float f[8];
-      xv[it].to_f(f);
-      const bool ok = (okmask >> it) & 1u;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = ok ? fmaxf(f[e] * sc[e] + sh[e], 0.f) : 0.f;
-      if constexpr (F32) {
-        u32x4 a, bq, hi, mid, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          a[e] = __float_as_uint(f[e]);
-          bq[e] = __float_as_uint(f[4 + e]);
-        }
-        split3_8(a, bq, hi, mid, lo);
-        *reinterpret_cast<u32x4*>(pb + plds[it]) = hi;
-        *reinterpret_cast<u32x4*>(pb + patch_b + plds[it]) = mid;
-        *reinterpret_cast<u32x4*>(pb + 2 * patch_b + plds[it]) = lo;
-      } else {
-        *reinterpret_cast<u32x4*>(pb + plds[it]) = pack8(f);
-      }
+      bnrelu_store<T>(pb, patch_b, plds[it], xv[it], (okmask >> it) & 1u, sc, sh);
     }
 #pragma unroll
     for (int j = 0; j < ZIT; ++j) {
@@ -253,7 +223,7 @@ __global__ __launch_bounds__(256) void preact_wgrad_kernel(PreactWgradParams p) 
 #pragma unroll
         for (int t = 0; t < NPL; ++t) {
           const char* ap = zb + t * dz_b + kb * (32 * ZROW) + aaddr;
-          a[t] = pw_frag(ap, ap + 4 * ZROW);
+          a[t] = frag_tr16(ap, ap + 4 * ZROW);
         }
         // the patch units of this lane's two pixels at tap (0, 0); pixels past the strip clamp into it
         int unit[2];
@@ -269,20 +239,11 @@ __global__ __launch_bounds__(256) void preact_wgrad_kernel(PreactWgradParams p) 
 #pragma unroll
           for (int j = 0; j < UPW; ++j) {
             const int bcol = (hf0 + j) * 2 + (p4 >> 1);
-            const uint32_t o0 = pw_off<VPP>(unit[0] + d, bcol) + bsub, o1 = pw_off<VPP>(unit[1] + d, bcol) + bsub;
+            const uint32_t o0 = patch_off<VPP>(unit[0] + d, bcol) + bsub, o1 = patch_off<VPP>(unit[1] + d, bcol) + bsub;
             u32x4 bb[NPL];
 #pragma unroll
-            for (int t = 0; t < NPL; ++t) bb[t] = pw_frag(pb + t * patch_b + o0, pb + t * patch_b + o1);
-            if constexpr (F32) {
-              acc[j][tap] = mfma_bf16(a[2], bb[0], acc[j][tap]);
-              acc[j][tap] = mfma_bf16(a[0], bb[2], acc[j][tap]);
-              acc[j][tap] = mfma_bf16(a[1], bb[1], acc[j][tap]);
-              acc[j][tap] = mfma_bf16(a[1], bb[0], acc[j][tap]);
-              acc[j][tap] = mfma_bf16(a[0], bb[1], acc[j][tap]);
-              acc[j][tap] = mfma_bf16(a[0], bb[0], acc[j][tap]);
-            } else {
-              acc[j][tap] = mfma16(__builtin_bit_cast(act16x8, a[0]), __builtin_bit_cast(act16x8, bb[0]), acc[j][tap]);
-            }
+            for (int t = 0; t < NPL; ++t) bb[t] = frag_tr16(pb + t * patch_b + o0, pb + t * patch_b + o1);
+            mfma_acc<F32>(a, bb, acc[j][tap]);
           }
         }
       }
@@ -325,53 +286,12 @@ __global__ __launch_bounds__(256) void preact_wgrad_kernel(PreactWgradParams p) 
   }
 }
 
-// dw[n][tap * C + c] += sum over the slabs of ws[slab][n][tap][c]. A block folds 16 consecutive elements: thread
-// (sl, el) sums slabs sl, sl + 16, ... of element el in slab order, then the 16 partial sums meet in LDS and are
-// added in sl order -- a fixed order, whatever the device
-__global__ __launch_bounds__(256) void preact_wgrad_fold_kernel(PreactWgradParams p) {
-  __shared__ float part[16][17];
-  const int el = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + el;
-  const int K = 9 * p.C;
-  const bool ok = idx < p.Nout * K;
-  const int n = ok ? idx / K : 0, k = ok ? idx - n * K : 0;
-  float sum = 0.f;
-  if (ok) {
-    const int tap = k / p.C, c = k - tap * p.C;
-    const int C32 = (p.C + 31) & ~31;
-    const size_t stride = (size_t)p.Nout * 9 * C32;
-    const float* src = p.ws + ((size_t)n * 9 + tap) * C32 + c;
-    for (int b = sl; b < p.nslabs; b += 16) sum += src[b * stride];
-  }
-  part[sl][el] = sum;
-  __syncthreads();
-  if (sl != 0 || !ok) return;
-  float t = part[0][el];
-#pragma unroll
-  for (int j = 1; j < 16; ++j) t += part[j][el];
-  p.dw[(size_t)n * p.ldw + k] += t;
-}
-
-template <typename T, int NRT, int NH>
-void pw_launch(const PreactWgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  // more than the default 64 KiB of dynamic LDS: raised on every launch, as preact3x3.hip does
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)preact_wgrad_kernel<T, NRT, NH>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PW_LDS_MAX);
-    if (e != hipSuccess) {
-      fprintf(stderr, "hcb preact_conv3x3_wgrad: cannot raise the dynamic LDS limit: %s\n", hipGetErrorString(e));
-      abort();
-    }
-  }
-  hipLaunchKernelGGL((preact_wgrad_kernel<T, NRT, NH>), grid, dim3(256), lds, st, p);
-}
-
 template <typename T, int NRT>
 void pw_launch_h(const PreactWgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
   if (p.C == 16)
-    pw_launch<T, NRT, 1>(p, grid, lds, st);
+    launch_big_lds(preact_wgrad_kernel<T, NRT, 1>, grid, lds, st, p, "preact_conv3x3_wgrad");
   else
-    pw_launch<T, NRT, 2>(p, grid, lds, st);
+    launch_big_lds(preact_wgrad_kernel<T, NRT, 2>, grid, lds, st, p, "preact_conv3x3_wgrad");
 }
 
 template <typename T>
@@ -384,21 +304,14 @@ void pw_launch_t(const PreactWgradParams& p, dim3 grid, size_t lds, hipStream_t 
     pw_launch_h<T, 4>(p, grid, lds, st);
 }
 
-// TF 'SAME' for a 3-wide window: output size and the leading pad
-void pw_same(int size, int s, int* out, int* lead) {
-  *out = (size + s - 1) / s;
-  const int total = (*out - 1) * s + 3 - size;
-  *lead = (total > 0 ? total : 0) / 2;
-}
-
 }  // namespace
 
 bool preact_conv3x3_wgrad_plan(int N, int H, int W, int C, int Nout, int s, bool f32, PreactWgradPlan* out) {
   if (!(C == 16 || C == 32 || C == 64) || !(Nout == 16 || Nout == 32 || Nout == 64) || !(s == 1 || s == 2)) return false;
   if (N < 1 || H < 1 || W < 1) return false;
   PreactWgradPlan pl{};
-  pw_same(H, s, &pl.P, &pl.pt);
-  pw_same(W, s, &pl.Q, &pl.pl);
+  same3(H, s, &pl.P, &pl.pt);
+  same3(W, s, &pl.Q, &pl.pl);
   if (pl.Q > PW_STRIP) return false;
   const int vpp = C == 16 ? 2 : 4, nrt = Nout / 16, nchunks = (C + 31) / 32;
   const int u = nrt * (vpp / 2), wu = u < 4 ? u : 4, ks = 4 / wu;
@@ -454,7 +367,8 @@ void launch_preact_conv3x3_wgrad(const PreactWgradParams& p0, hipStream_t st, bo
   else
     pw_launch_t<uint16_t>(p, grid, pl.lds_bytes, st);
   const int total = p.Nout * 9 * p.C;
-  hipLaunchKernelGGL(preact_wgrad_fold_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(wgrad_fold_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, p.ws, p.dw, p.C, p.ldw,
+                     p.nslabs, p.Nout, p.Nout);
 }
 
 }  // namespace hcb

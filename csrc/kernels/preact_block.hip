@@ -6,7 +6,7 @@
 // x [N][H][W] (row stride ldx), res / out [N][P][Q] (row strides ldr / ldo), C_in and Nout in {16, 32, 64}, s in
 // {1, 2}. a1, z1 and a2 never leave the chip. Both pads belong to the ACTIVATED maps: out-of-image positions of a1
 // and a2 are zero, not relu(shift). A sibling of preact3x3.hip (whose kernel stays the training / fp32 form): the
-// same 64-byte LDS unit and XOR swizzle, the same tap addressing, column tiles over the waves.
+// 64-byte LDS unit, XOR swizzle and patch store of patch3x3.h, the same tap addressing, column tiles over the waves.
 //
 // Work split. A workgroup of 4 waves owns a strip of TR whole output rows of one image; wave w computes column tile
 // w % NCT (NCT = Nout / 16) of the pixel tiles w / NCT + k * (4 / NCT) in both phases.
@@ -42,6 +42,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "patch3x3.h"
 
 namespace hcb {
 
@@ -51,11 +52,6 @@ constexpr int PB_MAXIT = 7;  // x-patch vectors (8 channels of one pixel) per th
 constexpr int PB_T1 = 3;     // 16-pixel MFMA tiles per wave, phase 1: (TR + 2) * Q <= 48 * (4 / NCT)
 constexpr int PB_T2 = 2;     // phase 2: TR * Q <= 32 * (4 / NCT)
 constexpr size_t PB_LDS_MAX = 160 * 1024;
-
-// byte offset of 16-byte column v of 64-byte unit `unit` (preact3x3.hip's swizzle)
-__device__ __forceinline__ uint32_t pb_off(int unit, int v) {
-  return (uint32_t)unit * 64u + (uint32_t)((v ^ ((unit >> 2) & 3)) << 4);
-}
 
 template <int NCT>
 __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) {
@@ -115,12 +111,12 @@ __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) 
 #pragma unroll
     for (int it = 0; it < WIT; ++it) {
       const int unit = (it * 256 + tid) >> 2;
-      if (unit < WUNITS) *reinterpret_cast<u32x4*>(wb + pb_off(unit, v)) = wv[it];
+      if (unit < WUNITS) *reinterpret_cast<u32x4*>(wb + patch_off(unit, v)) = wv[it];
     }
   };
 
   // ---- the x patch: chunk c global -> registers (xload), BN1 + ReLU, halo to zero -> LDS (xstore)
-  u32x4 xv[PB_MAXIT];
+  Act8<uint16_t> xv[PB_MAXIT];
   uint32_t xin = 0;  // bit it: vector `it` lies inside the image and below C
   auto xload = [&](int c) {
     const int cc = c * 32 + v * 8;
@@ -132,32 +128,18 @@ __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) 
       const int r = pp / p.PW, col = pp - r * p.PW;
       const int h = h0 + r, w = w0 + col;
       const bool ok = cok && pp < p.patch_pix && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
-      xv[it] = buf_load16(xr, ok ? (uint32_t)((((size_t)(n * p.H + h) * p.W + w) * p.ldx + cc) * 2u) : HCB_OOB);
+      xv[it].load(xr, ok ? (uint32_t)((((size_t)(n * p.H + h) * p.W + w) * p.ldx + cc) * 2u) : HCB_OOB);
       xin |= ok ? 1u << it : 0u;
     }
   };
   auto xstore = [&](int c) {
     char* pb = xpatch + (size_t)c * patch_b;
     float sc[8], sh[8];
-    const f32x4* cs = reinterpret_cast<const f32x4*>(coef1 + c * 32 + v * 8);
-    const f32x4* ch = reinterpret_cast<const f32x4*>(coef1 + Cr + c * 32 + v * 8);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      sc[e] = cs[0][e];
-      sc[4 + e] = cs[1][e];
-      sh[e] = ch[0][e];
-      sh[4 + e] = ch[1][e];
-    }
+    bn_coef_load8(coef1, Cr, c * 32 + v * 8, sc, sh);
 #pragma unroll
     for (int it = 0; it < PB_MAXIT; ++it) {
       const int pp = (it * 256 + tid) >> 2;
-      if (pp >= p.patch_pix) continue;
-      float f[8];
-      unpack8(xv[it], f);
-      const bool ok = (xin >> it) & 1u;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = ok ? fmaxf(f[e] * sc[e] + sh[e], 0.f) : 0.f;
-      *reinterpret_cast<u32x4*>(pb + pb_off(pp, v)) = pack8(f);
+      if (pp < p.patch_pix) bnrelu_store<uint16_t>(pb, patch_b, patch_off(pp, v), xv[it], (xin >> it) & 1u, sc, sh);
     }
   };
 
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) 
   lstorew(0);
   __syncthreads();
 
-  const uint32_t a0 = pb_off(ct * 16 + frow, fq);  // this lane's weight fragment of tap 0; tap t: + t * NW * 64
+  const uint32_t a0 = patch_off(ct * 16 + frow, fq);  // this lane's weight fragment of tap 0; tap t: + t * NW * 64
 
   // ---- phase 1: conv1 of rows [ra, rb) from the x patch
   f32x4 acc1[PB_T1];
@@ -210,7 +192,7 @@ __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) 
 #pragma unroll
       for (int ti = 0; ti < PB_T1; ++ti) {
         if (pw + NPW * ti >= nt1) continue;  // (wave-uniform)
-        const u32x4 bb = *reinterpret_cast<const u32x4*>(pb + pb_off(ub1[ti] + (tap / 3) * p.PW + tap % 3, fq));
+        const u32x4 bb = *reinterpret_cast<const u32x4*>(pb + patch_off(ub1[ti] + (tap / 3) * p.PW + tap % 3, fq));
         acc1[ti] = mfma16(__builtin_bit_cast(act16x8, a), __builtin_bit_cast(act16x8, bb), acc1[ti]);
       }
     }
@@ -232,7 +214,7 @@ __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) 
         u32x2 o2;
         o2[0] = pack2(f[0], f[1]);
         o2[1] = pack2(f[2], f[3]);
-        *reinterpret_cast<u32x2*>(ab + pb_off(unit, (j & 31) >> 3)) = o2;
+        *reinterpret_cast<u32x2*>(ab + patch_off(unit, (j & 31) >> 3)) = o2;
       }
     }
     lstorew((c + 1) & 1);
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(256) void preact_block_kernel(PreactBlockParams p) 
 #pragma unroll
       for (int ti = 0; ti < PB_T2; ++ti) {
         if (pw + NPW * ti >= nt2) continue;  // (wave-uniform)
-        const u32x4 bb = *reinterpret_cast<const u32x4*>(pb + pb_off(ub2[ti] + (tap / 3) * p.AW + tap % 3, fq));
+        const u32x4 bb = *reinterpret_cast<const u32x4*>(pb + patch_off(ub2[ti] + (tap / 3) * p.AW + tap % 3, fq));
         acc2[ti] = mfma16(__builtin_bit_cast(act16x8, a), __builtin_bit_cast(act16x8, bb), acc2[ti]);
       }
     }
@@ -294,13 +276,6 @@ struct PbPlan {
   size_t lds;
 };
 
-// TF 'SAME' for a 3-wide window: output size and the leading pad
-void pb_same(int size, int s, int* out, int* lead) {
-  *out = (size + s - 1) / s;
-  const int total = (*out - 1) * s + 3 - size;
-  *lead = (total > 0 ? total : 0) / 2;
-}
-
 // strip rows, patch sizes and LDS bytes for this problem; false for a shape the kernel does not take or one whose
 // one-row strip exceeds the tile, staging or LDS budget
 bool pb_plan(int H, int W, int C, int Nout, int s, PbPlan* pl) {
@@ -308,8 +283,8 @@ bool pb_plan(int H, int W, int C, int Nout, int s, PbPlan* pl) {
   if (H < 1 || W < 1) return false;
   pl->nct = Nout / 16;
   const int npw = 4 / pl->nct;
-  pb_same(H, s, &pl->P, &pl->pt);
-  pb_same(W, s, &pl->Q, &pl->pl);
+  same3(H, s, &pl->P, &pl->pt);
+  same3(W, s, &pl->Q, &pl->pl);
   const int Cr = (C + 31) & ~31, Nr = (Nout + 31) & ~31;
   pl->PW = (pl->Q - 1) * s + 3;
   pl->AW = pl->Q + 2;
@@ -331,21 +306,6 @@ bool pb_plan(int H, int W, int C, int Nout, int s, PbPlan* pl) {
   return false;
 }
 
-template <int NCT>
-void pb_launch(const PreactBlockParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  // more than the default 64 KiB of dynamic LDS: raised on every launch (a host-side attribute of the current
-  // device's function, no stream work), so every device gets it and a failure is seen here
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)preact_block_kernel<NCT>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PB_LDS_MAX);
-    if (e != hipSuccess) {
-      fprintf(stderr, "hcb preact_block: cannot raise the dynamic LDS limit: %s\n", hipGetErrorString(e));
-      abort();
-    }
-  }
-  hipLaunchKernelGGL((preact_block_kernel<NCT>), grid, dim3(256), lds, st, p);
-}
-
 }  // namespace
 
 bool preact_block_fits(int N, int H, int W, int C, int Nout, int stride) {
@@ -365,11 +325,11 @@ void launch_preact_block(const PreactBlockParams& p0, hipStream_t st) {
   p.strips_per_img = (p.P + p.TR - 1) / p.TR;
   const dim3 grid((unsigned)(p.N * p.strips_per_img));
   if (pl.nct == 1)
-    pb_launch<1>(p, grid, pl.lds, st);
+    launch_big_lds(preact_block_kernel<1>, grid, pl.lds, st, p, "preact_block");
   else if (pl.nct == 2)
-    pb_launch<2>(p, grid, pl.lds, st);
+    launch_big_lds(preact_block_kernel<2>, grid, pl.lds, st, p, "preact_block");
   else
-    pb_launch<4>(p, grid, pl.lds, st);
+    launch_big_lds(preact_block_kernel<4>, grid, pl.lds, st, p, "preact_block");
 }
 
 }  // namespace hcb

@@ -20,6 +20,7 @@ NOUT = 12
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 TOL = {"bf16": (1e-2, 2e-2), "fp16": (1e-2, 2e-2), "fp32": (3e-6, 1e-5)}  # (output, statistics)
 SHAPES = [
+    (1, 4, 4, 8),       # a quarter-filled chunk (channel masking) with the masked weight rows; three idle waves
     (2, 8, 8, 16),      # one chunk, two half-image strips, half the waves without a tile
     (1, 9, 12, 48),     # partial last chunk of 32, H = 5 + 4 strip rows, a partial last tile, W != H
     (2, 32, 32, 208),   # the widest block-1 layer of densenet40_k12: many chunks, the double buffer wraps
@@ -153,3 +154,46 @@ def test_dense_conv3x3_modes_with_store_pack(precision, mode):
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])  # bitwise reproducible
     st = runs[0][0][:, :, slot:slot + NOUT].double().sum(0)
     assert rel_err(st[0], ref.reshape(M, NOUT).sum(0)) < TOL[precision][1]
+
+
+@pytest.mark.parametrize("shape", [(2, 8, 8, 16), (1, 9, 12, 32)], ids=lambda s: "x".join(map(str, s)))
+def test_dense_matches_preact_bitwise(precision, shape):
+    """The dense layer's and the pre-activation conv's forward kernels are built from one set of helpers
+    (csrc/kernels/patch3x3.h). Per output pixel both sum K in the same
+    order (chunk, then tap) whatever the strip split -- 2 x 8 x 8: 4-row strips (dense) against 8-row strips (preact);
+    1 x 9 x 12: a short last strip and a partial last tile -- so on a problem both ops accept y is bitwise equal.
+    The statistics sum the strips in another order: they agree within the statistics bound of this file."""
+    N, H, W, C = shape
+    nout = 16
+    dt = DTYPES[precision]
+    M = N * H * W
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(N, H, W, C, generator=g)
+    gamma, beta = 0.5 + torch.rand(C, generator=g), 0.3 * torch.randn(C, generator=g)
+    w = (torch.randn(nout, 3, 3, C, generator=g) * math.sqrt(2.0 / 9 / nout)).to(DEV)
+    buf = torch.full((N, H, W, C + 16), 7.0).to(dt)
+    buf[..., :C] = x.to(dt)
+    d = buf[..., :C].double().reshape(M, C)
+    Rd = Fn.det_replicas(M)
+    acc = torch.zeros(Rd, 2, C + 16)
+    acc[0, 0, :C], acc[0, 1, :C] = d.sum(0).float(), (d * d).sum(0).float()
+    buf, acc, gamma, beta = buf.to(DEV), acc.to(DEV), gamma.to(DEV), beta.to(DEV)
+    acc_p = acc[:, :, :C].contiguous()
+    out = torch.zeros(N, H, W, nout, dtype=dt, device=DEV)
+    st_p = torch.zeros(Rd, 2, nout, device=DEV)
+    Fn.set_deterministic(True)
+    try:
+        sv = Fn.preact_conv3x3_forward(buf[..., :C], w, gamma, beta, EPS, out, stride=1, acc=acc_p, R=Rd,
+                                       out_stats=st_p, out_stats_R=Rd)
+        sv_mean, sv_inv = torch.zeros(C, device=DEV), torch.zeros(C, device=DEV)
+        Fn.dense_conv3x3_forward(buf, C, C, w, gamma, beta, EPS, acc=acc, R=Rd, saved_mean=sv_mean,
+                                 saved_invstd=sv_inv, stats=acc, stats_R=Rd)
+        torch.cuda.synchronize()
+    finally:
+        Fn.set_deterministic(False)
+    assert torch.equal(buf[..., C:], out), "y of the two ops differs"
+    assert torch.equal(sv_mean, sv.mean[:C]) and torch.equal(sv_inv, sv.invstd[:C])
+    st_d, st_q = acc[:, :, C:].sum(0), st_p.sum(0)
+    e1, e2 = rel_err(st_d[0], st_q[0]), rel_err(st_d[1], st_q[1])
+    print(f"{precision} {shape}: statistics dense against preact rel err {e1:.3e} {e2:.3e} (bound {TOL[precision][1]})")
+    assert e1 < TOL[precision][1] and e2 < TOL[precision][1]

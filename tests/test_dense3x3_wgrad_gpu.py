@@ -18,6 +18,7 @@ NOUT = 12
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 TOL = {"bf16": 1e-2, "fp16": 1e-2, "fp32": 3e-6}
 SHAPES = [
+    (1, 4, 8, 16),      # one strip, one slab: the fold adds a single partial; rows 12..15 of dw stay untouched
     (2, 8, 8, 16),      # less than one chunk, two strips of two K blocks
     (1, 9, 12, 48),     # a partial second chunk, one strip with a partial last K block, W != H
     (3, 16, 16, 104),   # several chunks, slabs of unequal strip counts, the double buffer wraps

@@ -17,6 +17,7 @@ EPS = 1e-5
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 TOL = {"bf16": 1e-2, "fp16": 1e-2, "fp32": 3e-6}
 SHAPES = [  # (N, H, W, C_in, Nout, stride)
+    (1, 4, 8, 16, 16, 1),     # one strip, one slab: the fold adds a single partial; one K block, three waves idle
     (2, 8, 8, 16, 16, 1),     # half a chunk; four waves split two K blocks
     (2, 6, 8, 64, 64, 1),     # two chunks, four row tiles (two units per wave), H != W
     (1, 32, 32, 16, 32, 2),   # the widest stride-2 patch (17 x 33), 128-pixel strips, halo rows shared between strips
