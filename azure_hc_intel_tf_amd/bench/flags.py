@@ -60,7 +60,8 @@ FLAGS: List[Flag] = [
     Flag("data_format", "NCHW", str, "logical layout (kernels run NHWC internally)", choices=["NCHW", "NHWC"]),
     Flag("optimizer", "sgd", str, "sgd | momentum | rmsprop | adam", choices=list(OPT_DEFAULTS)),
     Flag("forward_only", False, parse_bool, "inference-only benchmark (BN from the moving statistics, applied with "
-         "the residual add and ReLU in the conv GEMM's epilogue; HCB_FUSE_INFER_BN=0: separate BN passes)"),
+         "the residual add and ReLU in the conv GEMM's epilogue; HCB_FUSE_INFER_BN=0: separate BN passes; "
+         "HCB_FUSE_MBCONV_BLOCK=1: 16-bit mobilenet runs each inverted-residual block as one launch, off by default)"),
     Flag("eval", False, parse_bool, "evaluate instead of training: restore the latest checkpoint of --train_dir "
          "(without one: the seeded initial weights), run the validation split through the model in inference "
          "mode and print 'Accuracy @ 1 = ... Accuracy @ 5 = ... [N examples]' (top-1 / top-5 counted on the "

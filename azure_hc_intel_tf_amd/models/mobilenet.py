@@ -12,11 +12,16 @@ Architecture:
 
 The 1x1 convs are the implicit-GEMM kernels of every other model; the depthwise 3x3s are the stencil
 kernels of csrc/kernels/dwconv.hip (``nn.layers.DepthwiseConvBN``), and ReLU6 is the BN passes' upper
-clip. Hyper-parameters (default batch 32, base learning rate 0.005, BN decay 0.997, epsilon 1e-3)
+clip. 16-bit inference can run a whole bottleneck as one launch with the expanded activations resident in LDS
+(``Fn.mbconv_block_inference``, ``nn.layers.FUSE_MBCONV_BLOCK``; off by default, profiles/mobilenet_block.txt).
+Hyper-parameters (default batch 32, base learning rate 0.005, BN decay 0.997, epsilon 1e-3)
 follow upstream from memory; they are not pinned against the upstream source.
 """
 from __future__ import annotations
 
+import torch
+
+from ..nn import layers as L
 from ..nn.layers import ConvBN, DepthwiseConvBN, GlobalAvgPool, Logits, empty_act
 from ..ops import functional as Fn
 from .base import CNNModel
@@ -42,11 +47,26 @@ class InvertedResidual:
         self.project = ConvBN(ps, f"{name}/project", self.dw.out_shape, cout, 1, 1, relu=False, **BN)
         self.in_shape = in_shape
         self.out_shape = self.project.out_shape
+        self.t, self.stride = t, stride
 
     def layers(self):
         return [l for l in (self.expand, self.dw, self.project) if l is not None]
 
+    def _one_launch(self, x) -> bool:
+        """16-bit inference on native plain tensors of a geometry the block kernel's plan fits (FUSE_MBCONV_BLOCK)."""
+        return (L.FUSE_MBCONV_BLOCK and not self.dw.training and not self.project.training and Fn.native(x)
+                and not Fn.is_planes(x) and x.dtype != torch.float32
+                and Fn.mbconv_block_fits(x.shape, self.in_shape[2], self.t, self.out_shape[2], self.stride))
+
     def forward(self, x):
+        if self._one_launch(x):
+            e, d, p = self.expand, self.dw, self.project
+            out = empty_act((x.shape[0],) + tuple(self.out_shape), x.device)
+            return Fn.mbconv_block_inference(
+                x, e.w.data if e is not None else None, e._bn_params() if e is not None else None,
+                e.eps if e is not None else 0.0, d.w.data, d._bn_params(), d.eps, p.w.data, p._bn_params(), p.eps, out,
+                self.stride, res=x if self.identity else None, wpack_e=e.pack.pack if e is not None else None,
+                wpack_p=p.pack.pack)
         h = x
         if self.expand is not None:
             # the depthwise stencil reads a plain tensor: the expand BN writes one, not GEMM planes

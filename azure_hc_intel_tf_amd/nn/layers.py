@@ -1305,6 +1305,14 @@ FUSE_PREACT_WGRAD = os.environ.get("HCB_FUSE_PREACT_WGRAD", "0") == "1"
 # 0.03 %; profiles/resnet_cifar_v2_block.txt).
 FUSE_PREACT_BLOCK = _env_on("HCB_FUSE_PREACT_BLOCK")
 
+# 16-bit --forward_only MobileNet-v2: the WHOLE inverted-residual block -- 1x1 expand, BN + ReLU6, depthwise 3x3, BN +
+# ReLU6, 1x1 projection, BN and the identity add -- in one launch with the expanded activations resident in LDS
+# (csrc/kernels/mbconv_block.hip, Fn.mbconv_block_inference; models/mobilenet.py takes it where Fn.mbconv_block_fits).
+# False: the expand GEMM, bn_inference, dwconv_forward, bn_inference and the projection GEMM, five launches -- the A/B
+# partner. Training and fp32 never take it. Default OFF (``HCB_FUSE_MBCONV_BLOCK=1`` turns it on): see
+# profiles/mobilenet_block.txt for the measurements behind the default.
+FUSE_MBCONV_BLOCK = os.environ.get("HCB_FUSE_MBCONV_BLOCK", "0") == "1"
+
 
 class _PreActConv1(ConvBN):
     """conv1 of a pre-activation block: a ConvBN whose weight gradient PreActConv.backward may redirect to the fused

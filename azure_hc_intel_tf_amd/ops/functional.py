@@ -1772,6 +1772,89 @@ def preact_block_inference(x, w1, gamma1, beta1, rmean1, rvar1, eps1: float, w2,
     return out
 
 
+def pointwise_pack(w, dtype):
+    """The 16-bit GEMM operand of a 1x1 conv's fp32 kernel ``w`` [nout, 1, 1, C] outside a ParamStore (tools, tests): the
+    flat ``[nout * Kpad]`` pack, Kpad = C rounded up to 64 -- what ConvBN's pack holds for a 1x1."""
+    nout, C = w.shape[0], w.shape[-1]
+    full = torch.zeros((nout, _round_up(C, 64)), dtype=torch.float32, device=w.device)
+    full[:, :C] = w.reshape(nout, C)
+    return full.to(dtype).reshape(-1)
+
+
+def mbconv_block_fits(shape, c_in: int, t: int, cout: int, stride: int) -> bool:
+    """Whether the one-launch inference block (mbconv_block_inference's kernel) takes a block input of ``shape``
+    [N, H, W, ld] expanded ``t`` times: channels in multiples of 8 within its tile budget, stride 1 or 2, and a strip
+    of the map within its LDS budget."""
+    N, H, W = shape[:3]
+    if stride not in (1, 2) or t < 1 or c_in % 8 or cout % 8:
+        return False
+    return bool(_ext.ops().mbconv_block_fits([N, H, W, c_in, t, t * c_in, cout, c_in, cout, cout, 0, 0, int(stride)]))
+
+
+def mbconv_block_inference(x, w_exp, bn1, eps1: float, w_dw, bn2, eps2: float, w_proj, bn3, eps3: float, out,
+                           stride: int = 1, res=None, wpack_e=None, wpack_p=None):
+    """A whole MobileNet-v2 inverted-residual block at inference, on the block's input ``x`` [N, H, W, ld >= c_in]:
+
+        h1  = relu6(bn1(x @ w_exp))                w_exp [mid, 1, 1, c_in]; ``w_exp`` None (t = 1): h1 = x, mid = c_in
+        h2  = relu6(bn2(dw3x3_SAME(stride)(h1)))   w_dw fp32 [mid, 3, 3]
+        out[..., :cout] = bn3(h2 @ w_proj) [+ res[..., :cout]]          w_proj [cout, 1, 1, mid], no activation
+
+    ``bn*`` = (gamma, beta, moving mean, moving variance), bn(v) = gamma * (v - mean) / sqrt(var + eps) + beta;
+    relu6(v) = min(max(v, 0), 6). ``out`` (and ``res``, the identity shortcut: only with stride 1 and c_in == cout,
+    added in fp32) are [N, P, Q, ld >= cout], P = ceil(H / stride), Q = ceil(W / stride), of x's dtype; channels past
+    cout of out's rows are left alone; ``out`` overlaps neither ``x`` nor ``res``. 'SAME' is TensorFlow's
+    (``same_pads``) and pads the ACTIVATED h1: outside the image it is 0, not relu6(shift).
+
+    GPU (csrc/kernels/mbconv_block.hip): ONE launch on native 16-bit tensors (not fp32, not Planes); h1 and h2 stay in
+    LDS, rounded to 16 bits once each. ``wpack_e`` / ``wpack_p``: the ConvBN 16-bit packs of the two 1x1 convs
+    ([nout][Kpad]); without them the kernels are packed here (pointwise_pack: tools and tests). Scale / shift of the
+    three BatchNorms are derived in the kernel from the live parameter tensors, so a captured graph sees parameters
+    changed since capture. CPU / non-native tensors: the formula above in PyTorch at ``x``'s dtype, which is the
+    definition."""
+    N, H, W, _ = x.shape
+    cout, mid = w_proj.shape[0], w_proj.shape[-1]
+    c_in = w_exp.shape[-1] if w_exp is not None else mid
+    assert tuple(w_dw.shape) == (mid, 3, 3) and (w_exp is None or w_exp.shape[0] == mid), \
+        "mbconv_block_inference: w_exp is [mid, 1, 1, c_in], w_dw [mid, 3, 3], w_proj [cout, 1, 1, mid]"
+    if native(x):
+        pdt = torch.bfloat16 if x.dtype == torch.float32 else x.dtype
+        if w_exp is not None and wpack_e is None:
+            wpack_e = pointwise_pack(w_exp, pdt)
+        if wpack_p is None:
+            wpack_p = pointwise_pack(w_proj, pdt)
+        x, res_t, out_t = _pl(x), (_pl(res) if res is not None else None), _pl(out)  # (the op refuses Planes and fp32 by name)
+        _ext.ops().mbconv_block_inf(x, wpack_e if w_exp is not None else None, w_dw, wpack_p, res_t, out_t,
+                                    [N, H, W, c_in, mid // c_in if mid % c_in == 0 else 0, mid, cout, x.stride(-2),
+                                     res_t.stride(-2) if res_t is not None else 0, out_t.stride(-2),
+                                     _round_up(c_in, 64), _round_up(mid, 64), int(stride)],
+                                    list(bn1) if w_exp is not None else [], list(bn2), list(bn3), float(eps1),
+                                    float(eps2), float(eps3))
+        return out
+    P, Q = (H + stride - 1) // stride, (W + stride - 1) // stride
+    assert tuple(out.shape[:3]) == (N, P, Q) and out.shape[3] >= cout, "mbconv_block_inference: out is [N, P, Q, >= cout]"
+    assert res is None or (stride == 1 and c_in == cout), "mbconv_block_inference: res only with stride 1 and c_in == cout"
+    dt = x.dtype
+
+    def bn(t, params, eps):
+        gamma, beta, rmean, rvar = params
+        c = t.shape[-1]
+        return (t - rmean[:c].to(dt)) * (torch.rsqrt(rvar[:c] + eps) * gamma[:c]).to(dt) + beta[:c].to(dt)
+
+    h = x[..., :c_in]
+    if w_exp is not None:
+        h = bn(h @ w_exp.reshape(mid, c_in).to(dt).t(), bn1, eps1).clamp(0, 6)
+    (pt, pb), (pl, pr) = same_pads(H, 3, stride), same_pads(W, 3, stride)
+    h = F.pad(h.permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    h = F.conv2d(h, w_dw.reshape(mid, 1, 3, 3).to(dt), stride=stride, groups=mid).permute(0, 2, 3, 1)
+    h = bn(h, bn2, eps2).clamp(0, 6)
+    o = bn(h @ w_proj.reshape(cout, mid).to(dt).t(), bn3, eps3)
+    if res is not None:
+        at = torch.float32 if dt in (torch.bfloat16, torch.float16) else dt
+        o = (o.to(at) + res[..., :cout].to(at)).to(dt)
+    out[..., :cout] = o
+    return out
+
+
 def preact_wgrad_workspace(shape, c_in: int, nout: int, stride: int, dtype, device):
     """The caller-owned workspace of preact_conv3x3_wgrad for a block input of ``shape`` [N, H, W, ld]:
     [slabs * nout * 9 * round_up(c_in, 32)] fp32, never zeroed. The slab count depends on the shape alone."""

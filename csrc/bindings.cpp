@@ -1782,6 +1782,119 @@ void preact_block_inf(const Tensor& x, const Tensor& w1, const Tensor& w2, const
   hcb::launch_preact_block(p, cur_stream());
 }
 
+// ---- MobileNet-v2 inverted-residual block, 16-bit inference (mbconv_block.hip): out = bn3(relu6(bn2(dw3x3_SAME(stride)(
+// relu6(bn1(x @ we))))) @ wp) [+ res] in one launch. geom = [N, H, W, cin, t, mid, cout, ldx, ldr, ldo, Kpad1, Kpad2,
+// stride]: x the NHWC block input, res / out NHWC of ceil(H / stride) x ceil(W / stride) pixels and x's type; we / wp the
+// [mid][Kpad1] / [cout][Kpad2] 16-bit packs of the 1x1 convs (we absent exactly when t == 1), wd the fp32 [mid][3][3]
+// depthwise kernel; bn1 / bn2 / bn3 = [gamma, beta, moving mean, moving variance] (fp32, live; bn1 empty when t == 1)
+static bool mbconv_block_geom_fits(at::IntArrayRef g) {
+  TORCH_CHECK(g.size() == 13,
+              "hcb.mbconv_block_inf: geom = [N, H, W, cin, t, mid, cout, ldx, ldr, ldo, Kpad1, Kpad2, stride]");
+  const int64_t N = g[0], H = g[1], W = g[2], cin = g[3], t = g[4], mid = g[5], cout = g[6], s = g[12];
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "hcb.mbconv_block_inf: empty tensor");
+  TORCH_CHECK(s == 1 || s == 2, "hcb.mbconv_block_inf: stride must be 1 or 2, got ", s);
+  TORCH_CHECK(cin >= 8 && mid >= 8 && cout >= 8 && cin % 8 == 0 && mid % 8 == 0 && cout % 8 == 0,
+              "hcb.mbconv_block_inf: channels must be multiples of 8, got ", cin, " -> ", mid, " -> ", cout);
+  TORCH_CHECK(t >= 1 && mid == t * cin, "hcb.mbconv_block_inf: mid must be t * cin, got ", mid, " for t = ", t, ", cin = ", cin);
+  return H < (1 << 20) && W < (1 << 20) && cin < (1 << 20) && mid < (1 << 20) && cout < (1 << 20) &&
+         hcb::mbconv_block_fits((int)N, (int)H, (int)W, (int)cin, (int)mid, (int)cout, (int)s, t != 1);
+}
+
+bool mbconv_block_fits(at::IntArrayRef g) { return mbconv_block_geom_fits(g); }
+
+void mbconv_block_inf(const Tensor& x, const c10::optional<Tensor>& we, const Tensor& wd, const Tensor& wp,
+                      const c10::optional<Tensor>& res, const Tensor& out, at::IntArrayRef g, at::TensorList bn1,
+                      at::TensorList bn2, at::TensorList bn3, double eps1, double eps2, double eps3) {
+  const char* op = "mbconv_block_inf";
+  check_cuda(x, "x");
+  check_cuda(out, "out");
+  if (res.has_value()) check_cuda(*res, "res");
+  TORCH_CHECK(x.scalar_type() != at::kFloat && out.scalar_type() != at::kFloat &&
+                  (!res.has_value() || res->scalar_type() != at::kFloat),
+              "hcb.mbconv_block_inf: float32 tensors are not taken (16-bit inference only; fp32 runs the unfused chain)");
+  TORCH_CHECK(x.dim() == 4 && out.dim() == 4 && (!res.has_value() || res->dim() == 4),
+              "hcb.mbconv_block_inf: x, res and out are plain [N, H, W, C] tensors (not Planes)");
+  TORCH_CHECK(out.scalar_type() == x.scalar_type() && (!res.has_value() || res->scalar_type() == x.scalar_type()),
+              "hcb.mbconv_block_inf: x, res and out dtypes differ");
+  check_act(x, "x");
+  check_act(wp, "wp");
+  check_f32(wd, "wd");
+  const bool fits = mbconv_block_geom_fits(g);
+  const int64_t N = g[0], H = g[1], W = g[2], cin = g[3], t = g[4], mid = g[5], cout = g[6], ldx = g[7], ldr = g[8],
+                ldo = g[9], Kpad1 = g[10], Kpad2 = g[11], s = g[12];
+  TORCH_CHECK(we.has_value() == (t != 1), "hcb.mbconv_block_inf: the expand pack is given exactly when t != 1");
+  TORCH_CHECK(!res.has_value() || (s == 1 && cin == cout),
+              "hcb.mbconv_block_inf: res is the identity shortcut: only with stride 1 and cin == cout");
+  TORCH_CHECK(ldx % 8 == 0 && ldo % 8 == 0 && (!res.has_value() || ldr % 8 == 0),
+              "hcb.mbconv_block_inf: ld must be a multiple of 8, got ", ldx, " / ", ldr, " / ", ldo);
+  TORCH_CHECK(ldx >= cin && ldo >= cout && (!res.has_value() || ldr >= cout), "hcb.mbconv_block_inf: rows of ", ldx, " / ",
+              ldr, " / ", ldo, " channels do not hold cin = ", cin, " / cout = ", cout);
+  const int64_t P = (H + s - 1) / s, Q = (W + s - 1) / s;
+  TORCH_CHECK(x.size(0) == N && x.size(1) == H && x.size(2) == W && x.size(3) >= cin,
+              "hcb.mbconv_block_inf: x is not [N, H, W, >= cin] of geom");
+  TORCH_CHECK(out.size(0) == N && out.size(1) == P && out.size(2) == Q && out.size(3) >= cout,
+              "hcb.mbconv_block_inf: out must be [N, P, Q, >= cout] = [", N, ", ", P, ", ", Q, ", ", cout, "]");
+  TORCH_CHECK(!res.has_value() || (res->size(0) == N && res->size(1) == P && res->size(2) == Q && res->size(3) >= cout),
+              "hcb.mbconv_block_inf: res must be [N, P, Q, >= cout] = [", N, ", ", P, ", ", Q, ", ", cout, "]");
+  const auto rows_ok = [](const Tensor& a, int64_t ld) {
+    return a.stride(3) == 1 && a.stride(2) == ld && a.stride(1) == ld * a.size(2) && a.stride(0) == ld * a.size(2) * a.size(1);
+  };
+  TORCH_CHECK(rows_ok(x, ldx) && rows_ok(out, ldo) && (!res.has_value() || rows_ok(*res, ldr)),
+              "hcb.mbconv_block_inf: non-contiguous rows (channel stride must be 1, pixel stride ld)");
+  TORCH_CHECK(Kpad2 % 8 == 0 && Kpad2 >= mid && (t == 1 || (Kpad1 % 8 == 0 && Kpad1 >= cin)),
+              "hcb.mbconv_block_inf: Kpad must be a multiple of 8 >= the conv's input channels");
+  TORCH_CHECK(fits, "hcb.mbconv_block_inf: ", H, " x ", W, " x ", cin, " -> ", mid, " -> ", cout, " at stride ", s,
+              " does not fit the strip, tile and LDS budget of the kernel");
+  const int64_t xb = ((N * H * W - 1) * ldx + cin) * 2, ob = ((N * P * Q - 1) * ldo + cout) * 2,
+                rb = ((N * P * Q - 1) * ldr + cout) * 2, web = mid * Kpad1 * 2, wpb = cout * Kpad2 * 2, wdb = mid * 9 * 4;
+  check_act_rows(op, x, xb, "x");
+  check_act_rows(op, out, ob, "out");
+  check_act_rows(op, wp, wpb, "wp");
+  check_act_rows(op, wd, wdb, "wd");
+  TORCH_CHECK(wd.is_contiguous(), "hcb.mbconv_block_inf: wd must be a contiguous [mid, 3, 3] tensor");
+  const char *xp = (const char*)x.data_ptr(), *opp = (const char*)out.data_ptr();
+  TORCH_CHECK(!(xp < opp + ob && opp < xp + xb), "hcb.mbconv_block_inf: out aliases x (other workgroups still read the halo)");
+  if (res.has_value()) {
+    check_act_rows(op, *res, rb, "res");
+    const char* rp = (const char*)res->data_ptr();
+    TORCH_CHECK(!(rp < opp + ob && opp < rp + rb), "hcb.mbconv_block_inf: out aliases res");
+  }
+  if (we.has_value()) {
+    check_act(*we, "we");
+    check_act_rows(op, *we, web, "we");
+  }
+  TORCH_CHECK(bn1.size() == (t != 1 ? 4u : 0u) && bn2.size() == 4 && bn3.size() == 4,
+              "hcb.mbconv_block_inf: bn1 / bn2 / bn3 = [gamma, beta, moving mean, moving variance] (bn1 empty when t == 1)");
+  const float* v[12] = {};
+  for (int i = 0; i < 12; ++i) {
+    if (i < 4 && t == 1) continue;
+    const Tensor& a = i < 4 ? bn1[i] : i < 8 ? bn2[i - 4] : bn3[i - 8];
+    const char* name = i < 4 ? "bn1" : i < 8 ? "bn2" : "bn3";
+    check_f32(a, name);
+    TORCH_CHECK(a.is_contiguous() && a.numel() >= (i < 8 ? mid : cout), "hcb.mbconv_block_inf: ", name,
+                " vectors must be contiguous with one value per channel");
+    v[i] = a.data_ptr<float>();
+  }
+  hcb::MbconvBlockParams p{};
+  p.x = x.data_ptr();
+  p.res = res.has_value() ? res->data_ptr() : nullptr;
+  p.out = out.data_ptr();
+  p.we = we.has_value() ? we->data_ptr() : nullptr;
+  p.wp = wp.data_ptr();
+  p.wd = wd.data_ptr<float>();
+  p.gamma1 = v[0]; p.beta1 = v[1]; p.mean1 = v[2]; p.var1 = v[3];
+  p.gamma2 = v[4]; p.beta2 = v[5]; p.mean2 = v[6]; p.var2 = v[7];
+  p.gamma3 = v[8]; p.beta3 = v[9]; p.mean3 = v[10]; p.var3 = v[11];
+  p.eps1 = (float)eps1; p.eps2 = (float)eps2; p.eps3 = (float)eps3;
+  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.cin = (int)cin; p.mid = (int)mid; p.cout = (int)cout;
+  p.ldx = (int)ldx; p.ldr = (int)ldr; p.ldo = (int)ldo; p.Kpad1 = (int)Kpad1; p.Kpad2 = (int)Kpad2; p.stride = (int)s;
+  p.x_bytes = (uint32_t)xb;
+  p.we_bytes = we.has_value() ? (uint32_t)web : 0u;
+  p.wp_bytes = (uint32_t)wpb;
+  p.wd_bytes = (uint32_t)wdb;
+  hcb::launch_mbconv_block(p, cur_stream());
+}
+
 // ---- dense layer weight gradient (dense3x3_wgrad.hip): dw[n][tap * C + c] += sum dz[.., slot + n] *
 // relu(BN(x[.., c])) shifted by the tap. geom = [N, H, W, C, ldx, slot, ldz, Nout]: x the raw NHWC concat
 // buffer, dz the layer's 16 channels of the block's gradient buffer (a view: rows of ldz channels, the
@@ -2298,6 +2411,9 @@ HCB_TORCH_LIBRARY(hcb, m) {
   m.def("preact_block_inf(Tensor x, Tensor w1, Tensor w2, Tensor res, Tensor(a!) out, int[] geom, Tensor[] bn1, "
         "Tensor[] bn2, float eps1, float eps2) -> ()");
   m.def("preact_block_fits(int[] geom) -> bool", preact_block_fits);
+  m.def("mbconv_block_inf(Tensor x, Tensor? we, Tensor wd, Tensor wp, Tensor? res, Tensor(a!) out, int[] geom, Tensor[] bn1, "
+        "Tensor[] bn2, Tensor[] bn3, float eps1, float eps2, float eps3) -> ()");
+  m.def("mbconv_block_fits(int[] geom) -> bool", mbconv_block_fits);
   m.def("dense_conv3x3_dgrad(Tensor x, Tensor dz, Tensor(a!) gin, Tensor w, Tensor gamma, Tensor beta, Tensor saved_mean, "
         "Tensor saved_invstd, Tensor(b!) ws, Tensor(c!) dgamma, Tensor(d!) dbeta, int[] geom) -> ()");
   m.def("dense_conv3x3_dgrad_ws(int[] geom, bool f32) -> int", dense_conv3x3_dgrad_ws);
@@ -2377,6 +2493,7 @@ HCB_TORCH_LIBRARY_IMPL(hcb, CUDA, m) {
   m.impl("dense_conv3x3_wgrad", dense_conv3x3_wgrad);
   m.impl("preact_conv3x3_wgrad", preact_conv3x3_wgrad);
   m.impl("preact_block_inf", preact_block_inf);
+  m.impl("mbconv_block_inf", mbconv_block_inf);
   m.impl("dense_conv3x3_dgrad", dense_conv3x3_dgrad);
   m.impl("synth_labels", synth_labels);
   m.impl("bucket_pack", bucket_pack);

@@ -438,6 +438,31 @@ struct PreactBlockParams {
 bool preact_block_fits(int N, int H, int W, int C, int Nout, int stride);
 void launch_preact_block(const PreactBlockParams& p, hipStream_t st);
 
+// ---------------------------------------------------------------- MobileNet-v2 inverted-residual block, inference (mbconv_block.hip)
+// out = bn3(relu6(bn2(dw3x3_SAME(stride)(relu6(bn1(x @ We))))) @ Wp) [+ res] in ONE launch, 16-bit tensors only: x the
+// NHWC block input (row stride ldx), res / out NHWC [N][P][Q] (row strides ldr / ldo), we [mid][Kpad1] / wp
+// [cout][Kpad2] the 16-bit packs of the two 1x1 convs (we null: no expand, mid == cin and h1 = x), wd the fp32
+// [mid][3][3] depthwise kernel. The three BatchNorms take their moving statistics; scale / shift are derived in the
+// kernel from the live vectors. Channels are multiples of 8, cin <= 160 with an expand, cout <= 320.
+struct MbconvBlockParams {
+  const void* x;
+  const void* res;  // null: no identity add
+  void* out;
+  const void *we, *wp;
+  const float* wd;
+  const float *gamma1, *beta1, *mean1, *var1;  // [mid] (unused without an expand)
+  const float *gamma2, *beta2, *mean2, *var2;  // [mid]
+  const float *gamma3, *beta3, *mean3, *var3;  // [cout]
+  float eps1, eps2, eps3;
+  int N, H, W, cin, mid, cout, ldx, ldr, ldo, Kpad1, Kpad2, stride;
+  uint32_t x_bytes, we_bytes, wp_bytes, wd_bytes;
+  // set by the launcher
+  int P, Q, pt, pl, TR, strips_per_img, x_pix, HW, h1_pix, h2_pix, nk1, nkx, nch, nct, cw;
+};
+// whether the shape is one the kernel takes and a two-row strip of it fits the tile and LDS budget
+bool mbconv_block_fits(int N, int H, int W, int cin, int mid, int cout, int stride, bool expand);
+void launch_mbconv_block(const MbconvBlockParams& p, hipStream_t st);
+
 // ---------------------------------------------------------------- data
 void launch_synth_images(void* out, int64_t n_pix, int C, int Cpad, float mean, float std,
                          uint64_t seed, hipStream_t st, bool f32 = false);

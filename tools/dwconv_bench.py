@@ -41,12 +41,51 @@ def timed(fn, iters):
     return a.elapsed_time(b) * 1e3 / iters  # us
 
 
+def block_main(args):
+    """--block: every bottleneck of the 16-bit forward-only model, eager, the one-launch block op
+    (csrc/kernels/mbconv_block.hip, FUSE_MBCONV_BLOCK) against the unfused chain, interleaved round by round."""
+    from azure_hc_intel_tf_amd.nn import layers as L
+
+    N = args.batch
+    print(f"# batch {N}, {args.iters} forwards per round, median of {args.rounds} rounds, random data, eager")
+    print("# dtype   H  cin  mid cout s | chain us  block us  chain/block")
+    for name in ("bf16", "fp16"):
+        m = create_model("mobilenet", device="cuda", compute_dtype=name, seed=1)
+        for l in m.layers:
+            l.training = False
+        for b in m.blocks:
+            H, W, C = b.in_shape
+            x = torch.randn(N, H, W, C, device="cuda").to(m.act_dtype)
+            if not Fn.mbconv_block_fits(x.shape, C, b.t, b.out_shape[2], b.stride):
+                print(f"{name:5s} {H:4d} {C:4d} {b.dw.in_shape[2]:4d} {b.out_shape[2]:4d} {b.stride} | the plan refuses it")
+                continue
+
+            def run(on):
+                L.FUSE_MBCONV_BLOCK = on
+                return b.forward(x)
+
+            ops = {"chain": lambda: run(False), "block": lambda: run(True)}
+            for fn in ops.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in ops}
+            for _ in range(args.rounds):
+                for k, fn in ops.items():
+                    t[k].append(timed(fn, args.iters))
+            c, k = statistics.median(t["chain"]), statistics.median(t["block"])
+            print(f"{name:5s} {H:4d} {C:4d} {b.dw.in_shape[2]:4d} {b.out_shape[2]:4d} {b.stride} | {c:8.1f} {k:9.1f} {c / k:8.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--block", action="store_true", help="time the one-launch inverted-residual block against the chain")
     args = ap.parse_args()
+    if args.block:
+        return block_main(args)
     N = args.batch
     problems = [(b.dw.in_shape, b.dw.stride, b.dw.pads) for b in create_model("mobilenet", device="cpu").blocks]
     _ext.set_act("bf16")
